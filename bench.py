@@ -29,7 +29,14 @@ each proving its own traces (independent proofs, weak scaling, no data-path
 collective); the barrier / max-time reduction runs over RCCL. With N > 1 the
 `sharded` object times ONE T = 2^21 proof over all N GPUs (strong scaling).
 
-Objects beside the headline:
+A plain run sets up, warms up, times the steps and prints the result line
+(the headline fields alone). --dump-outputs DIR also writes what the timed
+pipeline returned in its last step: each context's proof bytes, one float32
+value per byte, as DIR/proof_ctx<i>.npy. The traces are seeded, so two builds
+run with the same arguments can be compared file by file. Everything below
+takes runs of its own and is measured only with --full.
+
+Objects beside the headline (--full):
   host_to_proof — the same pipeline with every proof uploading its own trace (PCIe)
   single_proof  — one proof at a time (latency), with the per-stage split
   roofline      — the dominant kernel, the longer of k_layer16 / k_forest16
@@ -378,6 +385,30 @@ def high_entropy_blocks(T: int, b: int, tau: int, seed: int):
     return partition(im, mv, hw, ws, b)
 
 
+DUMP_MAX_BYTES = 60_000_000  # of .npy data per --dump-outputs directory (under 64 MB with the headers)
+
+
+def dump_outputs(outdir: str, proofs, prefix: str = "", max_bytes: int = DUMP_MAX_BYTES) -> dict:
+    """Write the proof bytes the timed pipeline returned in its last step, one
+    file per context: `outdir`/<prefix>proof_ctx<i>.npy, float32, one value per
+    byte. `proofs` = [(trace index, proof bytes)] in context order. When the
+    arrays together would pass `max_bytes`, each keeps a fixed sample of its
+    positions (seeded by its length alone, ascending), the same from run to
+    run. Returns {file name: values written}."""
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    cap = max(1, max_bytes // (4 * max(1, len(proofs))))
+    written = {}
+    for i, (_, pb) in enumerate(proofs):
+        a = np.frombuffer(pb, dtype=np.uint8)
+        if a.size > cap:
+            a = a[np.sort(np.random.default_rng(a.size).choice(a.size, cap, replace=False))]
+        name = f"{prefix}proof_ctx{i}.npy"
+        np.save(os.path.join(outdir, name), a.astype(np.float32))
+        written[name] = int(a.size)
+    return written
+
+
 # SEZKP_BENCH_HOST_COMM=1: rehearse the N > 1 paths on ONE GPU (every rank on
 # device 0, gloo instead of RCCL, the sharded contexts' exchanges staged
 # through host memory): the code paths of `--gpus N`, not its numbers
@@ -391,6 +422,12 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beside the headline (host_to_proof, single_proof, rooflines, "
+                         "worst case, host rows, CPU baseline, configs, dist_ntt, sharded) and check the timed proofs "
+                         "against re-proofs and the oracle; a plain run times the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write each context's last timed proof to DIR/proof_ctx<i>.npy")
     ap.add_argument("--log-t", type=int, default=21, help="trace rows T = 2^log_t (N = 8T)")
     ap.add_argument("--tau", type=int, default=8)
     ap.add_argument("--b", type=int, default=512)
@@ -510,6 +547,52 @@ def main():
                 "(PCIe-inclusive rates are never value); SURVEY 8(d)'s t, host blocks -> proof bytes, is "
                 "host_to_proof on the same line")
 
+    def headline_record(proof_len):
+        return {
+            "metric": METRIC, "value": value, "unit": "field-elements/s", "n_gpus": world, "steps": args.steps,
+            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
+            "proofs_per_step": K, "ms_per_proof": dt / total * 1e3,
+            "scaling": "weak", "vs_baseline": None, "dtype": "u64",
+            "data": f"synthetic: the blocks `sezkp-cli simulate --t {T} --b {args.b} --tau {args.tau}` writes at seeds "
+                    f"42..{41 + n_tr} (reference generator + partition, bit-exact restatement)",
+            "config": {"workload": f"stark-v1 prove, T=2^{args.log_t} rows (N=2^{args.log_t + 3} LDE domain), "
+                                   f"b={args.b}, tau={args.tau}, trace resident in HBM when the timed region starts, "
+                                   "proof bytes on the host (host_to_proof beside it: every proof uploads its own "
+                                   "trace over PCIe)",
+                       "value_is": headline, "upload_bytes_per_proof": upload_bytes,
+                       "T": T, "N": N, "tau": args.tau, "b": args.b, "proof_bytes": proof_len,
+                       "proofs_in_flight_per_gpu": K, "distinct_traces": n_tr,
+                       "parallelism": f"replicas x{world}, {K} independent proofs in flight per GPU"
+                                      + (" (REHEARSAL: every rank on GPU 0, gloo + host-staged exchanges; not a "
+                                         "multi-GPU measurement)" if REHEARSE and world > 1 else "")},
+            "halves_ms_per_proof": halves_, "host_cpu_per_wall": cpu_frac,
+            "timing": "one continuous pipeline: warmup proofs run straight into the timed ones; the window runs "
+                      "from the last warmup proof's completion to the last proof's completion (steps x inflight "
+                      "proofs complete inside it), barrier + device sync around the run",
+        }
+
+    dumped = None
+    if args.dump_outputs:
+        dumped = dump_outputs(args.dump_outputs, resident_last, f"rank{rank}_" if world > 1 else "")
+    if not args.full:
+        # a plain run ends here: the headline alone (every other measurement
+        # and the proof checks take runs of their own: --full)
+        pipe.close()
+        for c in ctxs:
+            c.close()
+        for t in traces:
+            t.unpin()
+        if rank == 0:
+            out = headline_record(len(resident_last[0][1]))
+            if numa is not None:
+                out["numa"] = numa
+            if dumped is not None:
+                out["dumped_outputs"] = dumped
+            emit(out, args.detail)
+        if dist:
+            dist.destroy_process_group()
+        return
+
     # ---- beside it, SURVEY 8(d)'s t: host blocks -> proof bytes, every proof
     # stages its own trace over PCIe (the PCIe-inclusive rate; never `value`)
     last = resident_last
@@ -599,26 +682,7 @@ def main():
         if committed:
             roof["committed_stats_top_kernel"] = committed
         out = {
-            "metric": METRIC, "value": value, "unit": "field-elements/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": dt / args.steps * 1e3, "higher_is_better": True,
-            "proofs_per_step": K, "ms_per_proof": dt / total * 1e3,
-            "scaling": "weak", "vs_baseline": None, "dtype": "u64",
-            "data": f"synthetic: the blocks `sezkp-cli simulate --t {T} --b {args.b} --tau {args.tau}` writes at seeds "
-                    f"42..{41 + n_tr} (reference generator + partition, bit-exact restatement)",
-            "config": {"workload": f"stark-v1 prove, T=2^{args.log_t} rows (N=2^{args.log_t + 3} LDE domain), "
-                                   f"b={args.b}, tau={args.tau}, trace resident in HBM when the timed region starts, "
-                                   "proof bytes on the host (host_to_proof beside it: every proof uploads its own "
-                                   "trace over PCIe)",
-                       "value_is": headline, "upload_bytes_per_proof": upload_bytes,
-                       "T": T, "N": N, "tau": args.tau, "b": args.b, "proof_bytes": proof_len,
-                       "proofs_in_flight_per_gpu": K, "distinct_traces": n_tr,
-                       "parallelism": f"replicas x{world}, {K} independent proofs in flight per GPU"
-                                      + (" (REHEARSAL: every rank on GPU 0, gloo + host-staged exchanges; not a "
-                                         "multi-GPU measurement)" if REHEARSE and world > 1 else "")},
-            "halves_ms_per_proof": halves_, "host_cpu_per_wall": cpu_frac,
-            "timing": "one continuous pipeline: warmup proofs run straight into the timed ones; the window runs "
-                      "from the last warmup proof's completion to the last proof's completion (steps x inflight "
-                      "proofs complete inside it), barrier + device sync around the run",
+            **headline_record(proof_len),
             "proofs_consistent": consistent,
             "host_to_proof": host,
             "single_proof": {"value": N * nsp / dt1, "unit": "field-elements/s", "ms_per_proof": dt1 / nsp * 1e3,
@@ -653,6 +717,8 @@ def main():
     if rank == 0:
         if numa is not None:
             out["numa"] = numa
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         out["worst_case"] = worst
         out["host_rows"] = host_rows
         if not args.no_cpu_baseline and world == 1:
@@ -745,7 +811,7 @@ def compact_line(out: dict, detail_path) -> dict:
     measurement. Everything else stays in the detail file the line names."""
     line = _pick(out, ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better",
                        "scaling", "vs_baseline", "dtype", "data", "ms_per_proof", "proofs_consistent", "error",
-                       "sharded_value", "sharded_ms_per_proof", "sharded_speedup_vs_1gpu_proof"))
+                       "sharded_value", "sharded_ms_per_proof", "sharded_speedup_vs_1gpu_proof", "dumped_outputs"))
     cfg = out.get("config")
     if isinstance(cfg, dict):
         line["config"] = _pick(cfg, ("workload", "value_is", "T", "N", "tau", "b", "proof_bytes",

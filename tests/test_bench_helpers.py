@@ -55,6 +55,31 @@ def test_halves():
     assert b.halves([1.0], 0.0) is None
 
 
+def test_dump_outputs_whole_and_sampled(tmp_path):
+    """--dump-outputs: one float32 file per context holding the proof's bytes;
+    past the size cap a fixed sample of positions, the same in every run."""
+    import numpy as np
+    b = _bench()
+    rng = np.random.default_rng(3)
+    proofs = [(i, rng.integers(0, 256, 1000 + i, dtype=np.uint8).tobytes()) for i in range(3)]
+    w = b.dump_outputs(str(tmp_path / "a"), proofs)
+    assert w == {f"proof_ctx{i}.npy": 1000 + i for i in range(3)}
+    for i, (_, pb) in enumerate(proofs):
+        a = np.load(tmp_path / "a" / f"proof_ctx{i}.npy")
+        assert a.dtype == np.float32 and a.astype(np.uint8).tobytes() == pb
+    # 3 arrays within 1200 bytes of float32: 100 values each, a subsequence of the proof
+    w = b.dump_outputs(str(tmp_path / "b"), proofs, "rank1_", max_bytes=1200)
+    b.dump_outputs(str(tmp_path / "c"), proofs, "rank1_", max_bytes=1200)
+    assert set(w.values()) == {100}
+    for i, (_, pb) in enumerate(proofs):
+        a = np.load(tmp_path / "b" / f"rank1_proof_ctx{i}.npy")
+        assert a.dtype == np.float32 and a.nbytes == 400
+        assert np.array_equal(a, np.load(tmp_path / "c" / f"rank1_proof_ctx{i}.npy"))
+        it = iter(pb)
+        assert all(any(int(v) == x for x in it) for v in a)  # in order, from the proof
+    assert b.DUMP_MAX_BYTES < 64_000_000
+
+
 def test_stdout_line_is_bounded_and_parseable():
     """the driver could not read round 4's 25.7 KB line. The
     formatter applied to that round's full record must give a json.loads-clean

@@ -2,7 +2,7 @@
 set -euo pipefail
 O=gpurun_out/kab
 mkdir -p $O
-B="python3 bench.py --steps 80 --no-cpu-baseline --no-configs --no-worst-case --no-host-rows --no-host-to-proof --no-sharded --dntt-log-n 0"
+B="python3 bench.py --full --steps 80 --no-cpu-baseline --no-configs --no-worst-case --no-host-rows --no-host-to-proof --no-sharded --dntt-log-n 0"
 : > $O/ab.txt
 for rep in 1 2 3; do
   for k in 3 4 2; do

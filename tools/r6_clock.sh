@@ -8,7 +8,7 @@ export TMPDIR=/tmp
 O=gpurun_out/${R6_OUT:-clock}
 mkdir -p $O
 C="SQ_INSTS_VALU SQ_WAVES SQ_INSTS_SALU SQ_INSTS_LDS SQ_ACTIVE_INST_VALU SQ_WAVE_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE"
-B="python3 bench.py --steps 6 --warmup 2 --no-cpu-baseline --no-configs --no-worst-case --no-host-to-proof --no-host-rows --no-sharded --dntt-log-n 0"
+B="python3 bench.py --full --steps 6 --warmup 2 --no-cpu-baseline --no-configs --no-worst-case --no-host-to-proof --no-host-rows --no-sharded --dntt-log-n 0"
 timeout -s KILL 150 rocprofv3 --pmc $C --output-format csv -d $O/valu_if1 -o run -- $B --inflight 1 --detail $O/if1.json > $O/valu_if1.log 2>&1
 echo "if1 ok"
 timeout -s KILL 150 rocprofv3 --pmc $C --output-format csv -d $O/valu_if3 -o run -- $B --detail $O/if3.json > $O/valu_if3.log 2>&1

@@ -7,5 +7,5 @@ O=gpurun_out/final
 mkdir -p $O
 timeout -k 10 900 python -u -m pytest tests -m gpu -v --timeout 300 --timeout-method thread > $O/gpu_tests.log 2>&1
 echo "tests ok"
-timeout -k 10 600 python -u bench.py --detail $O/bench_detail.json > $O/bench_default.json 2> $O/bench_default.err
+timeout -k 10 600 python -u bench.py --full --detail $O/bench_detail.json > $O/bench_default.json 2> $O/bench_default.err
 echo "bench ok"

@@ -11,5 +11,5 @@ if [ -n "${1:-}" ]; then
 fi
 timeout -k 10 120 python -u tools/c2_probe.py 20 400 > $O/c2.txt 2>&1
 echo "c2 ok"
-timeout -k 10 300 python -u bench.py --steps 100 --no-cpu-baseline --no-worst-case --no-host-rows --detail $O/detail.json > $O/bench.json 2> $O/bench.err
+timeout -k 10 300 python -u bench.py --full --steps 100 --no-cpu-baseline --no-worst-case --no-host-rows --detail $O/detail.json > $O/bench.json 2> $O/bench.err
 echo "bench ok"
