@@ -163,6 +163,32 @@ int32_t sezkp_ctx_prove_async(sezkp_ctx* ctx, const uint8_t manifest_root[32], u
 int32_t sezkp_ctx_wait(sezkp_ctx* ctx, const uint8_t** data, size_t* len, char* err, size_t err_len);
 /* Device hipStream_t of the context (as void*), for external timing. */
 void* sezkp_ctx_stream(const sezkp_ctx* ctx);
+/* The dictionary commitment's plan of the last completed prove, one entry per
+ * dictionary column (input_mv and every tape's mv, has_write flag, wsym and
+ * head), in column order: which kernel form committed and opened it. The
+ * entries are copied from the device only when this is called. Returns the
+ * number written (0 before the first prove of an upload, and always with
+ * SEZKP_NO_DICT=1), SEZKP_E_INVALID while a proof is in flight. Works on
+ * sharded contexts (this rank's plans).
+ * Test hook: SEZKP_TEST_DICT_PLAN_ROWS_LOG=<v> (read per prove) makes the
+ * planner choose K and a as on a device with 2^v rows, whatever the trace's
+ * size, so small traces run the forms of the largest shapes; the proof bytes
+ * do not depend on it. On a device with fewer than 2^16 rows v is lowered to
+ * 20 + max(0, log2(rows) - 14), so that a commit workgroup (256 lanes of
+ * 2^(6 + a) rows) is never partly filled at a > 0, as in production. Not for
+ * production: it only slows a small trace. */
+typedef struct sezkp_dict_plan_info {
+  uint32_t col;    /* column index (commitment order) */
+  uint32_t kind;   /* 0 input_mv, 3 mv, 4 write flag, 5 wsym, 6 head */
+  uint32_t tape;
+  int32_t K;       /* table level gathered by the commit (-1: leaves hashed) */
+  uint32_t a;      /* rows per commit lane = 2^(6 + a) */
+  uint32_t delta;  /* 1: head delta plan (4-row groups from head + 3 moves) */
+  uint32_t R;      /* range size max - min + 1 (0: more than 65536) */
+  uint32_t dR;     /* delta plan: range size of the tape's moves, else 0 */
+  int64_t min;     /* smallest raw value of the column on this device's rows */
+} sezkp_dict_plan_info;
+int32_t sezkp_ctx_dict_plans(const sezkp_ctx* ctx, sezkp_dict_plan_info* out, int32_t max);
 
 /* ------------------------------------------------ sharded proving (one proof, P GPUs)
  * One process per GPU; every rank uploads the same blocks and calls prove()
@@ -234,7 +260,9 @@ int32_t sezkp_ctx_dist_ntt(sezkp_ctx* ctx, uint64_t* local, uint64_t* scratch, u
 /* In-place NTT (dir=+1 forward, -1 inverse incl. n^-1), natural -> natural:
  * ntt.rs:79-155. `scratch` (2^log_n elements, clobbered) is required below 2^8 points and
  * may be null from 2^8 up; given at 2^19..2^22, the transform runs out of place through it
- * and needs no bit-reversal pass (distinct from d). Null device pointers are rejected (SEZKP_E_INVALID) here and in
+ * and needs no bit-reversal pass (distinct from d; scratch == d counts as null at every size, so it is
+ * SEZKP_E_INVALID below 2^8 points, with d untouched). Without scratch the transform is a DIF in place plus an
+ * in-place bit reversal, up to 2^28 points. Null device pointers are rejected (SEZKP_E_INVALID) here and in
  * every kernel-level entry point below, before anything is launched. */
 int32_t sezkp_gl_ntt(uint64_t* d, uint64_t* scratch, uint32_t log_n, int32_t dir, void* stream);
 /* Coset LDE + DEEP (deep_coset_lde_stream, lde.rs:42-97): evals[2^log_n]

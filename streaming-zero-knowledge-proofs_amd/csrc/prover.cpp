@@ -214,6 +214,8 @@ struct sezkp_ctx {
   int n_dict = 0;
   int64_t* d_dpart = nullptr;
   DictPlan* d_dplans = nullptr;
+  std::vector<sezkp_dict_plan_info> dict_info;  // col / kind / tape of each dictionary column (sezkp_ctx_dict_plans)
+  bool have_plans = false;           // d_dplans holds the plans of a completed prove of this upload
   uint32_t* d_dtabs = nullptr;
   uint32_t* d_dlev = nullptr;        // dictionary columns' chunk levels 6..9 (openings)
   std::vector<uint32_t> dict_of;     // column -> dictionary index or NO_DICT
@@ -753,6 +755,13 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
       for (size_t i = 0; i < dcols.size(); i++)
         if (tm[dcols[i].col].kind == 3 && tm[dcols[i].col].tape == tm[h.col].tape) h.mv = (uint32_t)i;
   n_dict = (int)dcols.size();
+  have_plans = false;
+  dict_info.assign(dcols.size(), sezkp_dict_plan_info{});
+  for (size_t i = 0; i < dcols.size(); i++) {
+    dict_info[i].col = dcols[i].col;
+    dict_info[i].kind = tm[dcols[i].col].kind;
+    dict_info[i].tape = tm[dcols[i].col].tape;
+  }
   d_dcols = dalloc<DictCol>(dcols.size() + 1);
   up(d_dcols, dcols.data(), dcols.size());
   d_dpart = dalloc<int64_t>(2 * dcols.size() * ((n + 4095) / 4096) + 2);
@@ -1141,6 +1150,7 @@ size_t sezkp_ctx::prove(const uint8_t mroot[32]) {
 
 size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded"};
+  have_plans = false;
   // the trace image was fixed by take_staged() in the public entry point that
   // started this proof (for prove_async: before the worker runs, so a stage()
   // issued right after prove_async fills the other slot, never this one)
@@ -1242,6 +1252,23 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     const long v = atol(cap);
     if (v >= 1 && v <= (long)DICT_CAP) dict_tab_cap = (uint32_t)v;
   }
+  // test hook: plan the dictionary columns as on a device with 2^v rows
+  // (SEZKP_TEST_DICT_PLAN_ROWS_LOG=<v>; read per prove), so small traces run
+  // the level / lane forms that only 2^21 rows and more select
+  uint64_t dict_plan_rows = 0;
+  if (const char* pr = getenv("SEZKP_TEST_DICT_PLAN_ROWS_LOG")) {
+    long v = atol(pr);
+    // a device with 2^v rows plans up to 2^(6 + a) rows per lane, a =
+    // v - 20 (0..2), and production then has at least 2^(14 + a) rows per
+    // device: every 256-lane commit workgroup is full. Keep the hook inside
+    // that space: with fewer real rows v is lowered until a full workgroup
+    // fits (a partly filled workgroup at a > 0 is a form nothing plans)
+    int lg = 0;
+    while ((2ULL << lg) <= row_hi - row_lo) lg++;
+    const long v_max = lg >= 16 ? 40 : 20 + (lg > 14 ? lg - 14 : 0);
+    if (v > v_max) v = v_max;
+    if (v >= COL_CHUNK_LOG2 && v <= 40) dict_plan_rows = 1ULL << v;
+  }
   const int nguard = sharded ? comm->world : 1;
   auto check_guards = [&](const uint32_t* g_h, int ng) {
     for (int r = 0; r < ng; r++) {
@@ -1330,7 +1357,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // (the commit of the K <= 2 columns on a third stream beside table levels
     // 3..4 measured slower, round 6: profiles/r06/ab/dict_split_streams_ab.txt)
     ok(launch_dict_commit(st, T, d_tmpl, d_dcols, n_dict, d_dpart, d_dplans, d_dtabs, d_outer, outer_stride, row_lo,
-                          row_hi - row_lo, d_dlev, dict_tab_cap),
+                          row_hi - row_lo, d_dlev, dict_tab_cap, dict_plan_rows),
        "col_commit_dict");
     HIP_OR_THROW(hipStreamWaitEvent(st, ev_cols, 0));
     // test hook: SEZKP_DEBUG_TRIP_GUARD=<rank> sets that rank's guard word, to
@@ -1824,6 +1851,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   host_ms[1] = t_sync;
   host_ms[2] = t_last;
   host_ms[3] = std::chrono::duration<double, std::milli>(t_end - t_ser).count();
+  have_plans = true;  // d_dplans: this proof's plans (sezkp_ctx_dict_plans)
   return out;
 }
 
@@ -2104,6 +2132,31 @@ int32_t sezkp_ctx_stage_times(const sezkp_ctx* ctx, double* out_ms, int32_t max)
   return cnt;
 }
 void* sezkp_ctx_stream(const sezkp_ctx* ctx) { return ctx ? (void*)ctx->st : nullptr; }
+int32_t sezkp_ctx_dict_plans(const sezkp_ctx* cctx, sezkp_dict_plan_info* out, int32_t max) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || (max > 0 && !out) || max < 0) return SEZKP_E_INVALID;
+  if (ctx->busy()) return SEZKP_E_INVALID;  // the plans are rewritten by the proof in flight
+  if (!ctx->loaded || !ctx->have_plans || ctx->n_dict == 0) return 0;
+  const int32_t cnt = std::min<int32_t>(max, ctx->n_dict);
+  if (cnt == 0) return 0;
+  std::vector<DictPlan> pl((size_t)cnt);
+  if (hipSetDevice(ctx->device) != hipSuccess ||
+      hipMemcpy(pl.data(), ctx->d_dplans, (size_t)cnt * sizeof(DictPlan), hipMemcpyDeviceToHost) != hipSuccess) {
+    (void)hipGetLastError();
+    return SEZKP_E_DEVICE;
+  }
+  for (int32_t i = 0; i < cnt; i++) {
+    sezkp_dict_plan_info& o = out[i];
+    o = ctx->dict_info[(size_t)i];
+    o.K = pl[i].K;
+    o.a = pl[i].a;
+    o.delta = pl[i].delta;
+    o.R = pl[i].R;
+    o.dR = pl[i].delta ? pl[i].dR : 0;
+    o.min = pl[i].min;
+  }
+  return cnt;
+}
 int32_t sezkp_ctx_comm_stats(const sezkp_ctx* ctx, sezkp_comm_stat* out, int32_t max) {
   if (!ctx || !out || max <= 0) return 0;
   int32_t cnt = 0;
@@ -2227,6 +2280,9 @@ int32_t sezkp_gl_ntt(uint64_t* d, uint64_t* scratch, uint32_t log_n, int32_t dir
     HIP_OR_THROW(hipGetDevice(&dev));
     const NttTables& T = tables_for_device(dev);
     hipStream_t st = (hipStream_t)stream;
+    // scratch == d is no scratch: below 2^8 points the out-of-place permutation
+    // would otherwise read and write the same buffer
+    if (scratch == d) scratch = nullptr;
     if (log_n > 28 || (dir != 1 && dir != -1) || !d || (log_n < 8 && !scratch)) return SEZKP_E_INVALID;
     if (log_n == 0) return SEZKP_OK;
     const bool inv = dir < 0;

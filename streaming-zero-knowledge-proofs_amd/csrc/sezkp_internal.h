@@ -283,13 +283,16 @@ hipError_t launch_col_commit(hipStream_t st, const TraceDev& T, const ColTemplat
 hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
                               int ndict, int64_t* d_part, DictPlan* d_plans, uint32_t* d_dtabs, uint32_t* outer_nodes,
                               uint64_t outer_stride_nodes, uint64_t row0, uint64_t nrows, uint32_t* d_dlev,
-                              uint32_t tab_cap = DICT_CAP);
+                              uint32_t tab_cap = DICT_CAP, uint64_t plan_rows = 0);
 // the same in three steps, so the commit of the columns whose table level K
 // is built early can run beside the later levels: ranges + plans, table
-// levels [lvl_lo, lvl_hi), and the commit of the columns with kmin <= K <= kmax
+// levels [lvl_lo, lvl_hi), and the commit of the columns with kmin <= K <= kmax.
+// plan_rows != 0 (test hook SEZKP_TEST_DICT_PLAN_ROWS_LOG): the planner prices
+// the levels and sizes the lanes as on a device with plan_rows rows; the
+// ranges are still those of rows [row0, row0 + nrows)
 hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
                                int ndict, int64_t* d_part, DictPlan* d_plans, uint64_t row0, uint64_t nrows,
-                               uint32_t tab_cap = DICT_CAP);
+                               uint32_t tab_cap = DICT_CAP, uint64_t plan_rows = 0);
 hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
                               const DictPlan* d_plans, uint32_t* d_dtabs, int lvl_lo, int lvl_hi);
 hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,

@@ -1613,7 +1613,7 @@ static hipError_t dict_shape_ok(const TraceDev& T, uint64_t row0, uint64_t nrows
 }
 hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
                                int ndict, int64_t* d_part, DictPlan* d_plans, uint64_t row0, uint64_t nrows,
-                               uint32_t tab_cap) {
+                               uint32_t tab_cap, uint64_t plan_rows) {
   if (ndict == 0) return hipSuccess;
   hipError_t e = dict_shape_ok(T, row0, nrows);
   if (e != hipSuccess) return e;
@@ -1625,8 +1625,8 @@ hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTempl
   hipLaunchKernelGGL(k_dict_range, dim3(nparts, ndict), dim3(TR_THREADS), 0, st, T, d_tmpl, d_dcols, d_part, nparts,
                      row0, row0 + nrows, sweeps);
   if ((e = hipGetLastError()) != hipSuccess) return e;
-  hipLaunchKernelGGL(k_dict_plan, dim3(ndict), dim3(TR_THREADS), 0, st, d_part, nparts, T.n, nrows, d_dcols, d_plans,
-                     tab_cap);
+  hipLaunchKernelGGL(k_dict_plan, dim3(ndict), dim3(TR_THREADS), 0, st, d_part, nparts, T.n,
+                     plan_rows ? plan_rows : nrows, d_dcols, d_plans, tab_cap);
   return hipGetLastError();
 }
 hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
@@ -1661,8 +1661,8 @@ hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColT
 hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
                               int ndict, int64_t* d_part, DictPlan* d_plans, uint32_t* d_dtabs, uint32_t* outer_nodes,
                               uint64_t outer_stride_nodes, uint64_t row0, uint64_t nrows, uint32_t* d_dlev,
-                              uint32_t tab_cap) {
-  hipError_t e = launch_dict_prepare(st, T, d_tmpl, d_dcols, ndict, d_part, d_plans, row0, nrows, tab_cap);
+                              uint32_t tab_cap, uint64_t plan_rows) {
+  hipError_t e = launch_dict_prepare(st, T, d_tmpl, d_dcols, ndict, d_part, d_plans, row0, nrows, tab_cap, plan_rows);
   if (e == hipSuccess && ndict) e = launch_dict_levels(st, d_tmpl, d_dcols, ndict, d_plans, d_dtabs, 0, DICT_LEVELS);
   if (e == hipSuccess)
     e = launch_dict_commit_cols(st, T, d_tmpl, d_dcols, ndict, d_plans, d_dtabs, outer_nodes, outer_stride_nodes, row0,

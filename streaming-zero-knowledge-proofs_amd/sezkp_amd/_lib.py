@@ -35,12 +35,18 @@ EXPORTS = [
     "sezkp_merkle_build", "sezkp_merkle_paths", "sezkp_manifest_frontier_root", "sezkp_ctx_comm_stats",
     "sezkp_fs_xof", "sezkp_ctx_upload_rows", "sezkp_shard_rows", "sezkp_blocks_decode_jsonl_meta",
     "sezkp_blocks_line_offsets", "sezkp_manifest_leaf_hashes", "sezkp_merkle_root_of_leaves",
-    "sezkp_ctx_create_sharded_solo", "sezkp_blocks_decode_jsonl_lines",
+    "sezkp_ctx_create_sharded_solo", "sezkp_blocks_decode_jsonl_lines", "sezkp_ctx_dict_plans",
 ]
 
 
 class CommStat(C.Structure):
     _fields_ = [("name", C.c_char * 32), ("bytes", C.c_uint64), ("ms", C.c_double)]
+
+
+class DictPlanInfo(C.Structure):
+    _fields_ = [("col", C.c_uint32), ("kind", C.c_uint32), ("tape", C.c_uint32), ("K", C.c_int32),
+                ("a", C.c_uint32), ("delta", C.c_uint32), ("R", C.c_uint32), ("dR", C.c_uint32),
+                ("min", C.c_int64)]
 
 
 class SezkpError(RuntimeError):
@@ -117,6 +123,7 @@ def _load():
     L.sezkp_ctx_stream.restype = C.c_void_p
     L.sezkp_ctx_comm_stats.argtypes = [C.c_void_p, C.POINTER(CommStat), C.c_int32]
     L.sezkp_ctx_stream.argtypes = [C.c_void_p]
+    L.sezkp_ctx_dict_plans.argtypes = [C.c_void_p, C.POINTER(DictPlanInfo), C.c_int32]
     L.sezkp_gl_ntt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
     L.sezkp_gl_coset_lde_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]

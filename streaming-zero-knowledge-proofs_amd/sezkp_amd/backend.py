@@ -191,6 +191,20 @@ class ProverContext:
                         "GBs": (b / ms / 1e6) if ms > 0 else None})
         return out
 
+    def dict_plans(self) -> list:
+        """The dictionary commitment's plan of the last prove, one dict per
+        dictionary column: {col, kind, tape, K, a, delta, R, dR, min}
+        (sezkp_ctx_dict_plans; empty with SEZKP_NO_DICT=1 or below 1024 rows)."""
+        from ._lib import DictPlanInfo
+        cap = 1 + 4 * self.tau  # input_mv and, per tape, mv / write flag / wsym / head
+        buf = (DictPlanInfo * cap)()
+        n = lib.sezkp_ctx_dict_plans(self._h, buf, cap)
+        if n < 0:
+            why = {-1: "a proof is in flight on this context (or the context is closed)",
+                   -2: "copying the plans from the device failed"}.get(n, "unexpected return code")
+            raise SezkpError(n, f"dict_plans: {why}")
+        return [{f: int(getattr(buf[i], f)) for f, _ in DictPlanInfo._fields_} for i in range(n)]
+
     def dist_ntt(self, local, scratch=None, inverse: bool = False, sync: bool = True):
         """Distributed four-step NTT of n = world * local.numel() points, in
         place on `local` (a device u64/i64 tensor; layouts in sezkp_stark.h,

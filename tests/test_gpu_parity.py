@@ -32,39 +32,94 @@ def _host(t) -> np.ndarray:
     return t.cpu().numpy().view(np.uint64)
 
 
+def _ntt_scratch_modes(torch, product, x, want, log_n, stream=False):
+    """sezkp_gl_ntt on `x` without a scratch buffer (scratch = NULL) and with
+    scratch == d (documented as no scratch): forward values equal `want` (the
+    oracle's transform, computed once by the caller) and the inverse returns
+    `x`, compared on the device. Below 2^8 points both are SEZKP_E_INVALID
+    and leave the data untouched. stream=True also runs both scratch forms
+    (given / none) on a non-default stream."""
+    lib = product.lib
+    d_x, d_want = _dev(torch, x), _dev(torch, want)
+    for alias in (False, True):
+        d = d_x.clone()
+        sp = d.data_ptr() if alias else None
+        torch.cuda.synchronize()
+        for direction, expect in ((1, d_want), (-1, d_x)):
+            rc = lib.sezkp_gl_ntt(d.data_ptr(), sp, log_n, direction, None)
+            torch.cuda.synchronize()
+            if log_n < 8:
+                assert rc == -1, (log_n, alias, direction)  # SEZKP_E_INVALID
+                assert torch.equal(d, d_x)
+            else:
+                assert rc == 0, (log_n, alias, direction)
+                assert torch.equal(d, expect), (log_n, alias, direction)
+    if stream:
+        s = torch.cuda.Stream()
+        for with_scratch in (True, False):
+            if log_n < 8 and not with_scratch:
+                continue
+            d = d_x.clone()
+            scratch = torch.empty_like(d) if with_scratch else None
+            torch.cuda.synchronize()
+            for direction, expect in ((1, d_want), (-1, d_x)):
+                assert lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr() if with_scratch else None, log_n, direction,
+                                        s.cuda_stream) == 0
+                s.synchronize()
+                assert torch.equal(d, expect), (log_n, with_scratch, direction)
+
+
 @pytest.mark.parametrize("log_n", list(range(1, 21)))
 def test_ntt_roundtrip_matches_oracle(gpu_ok, product, oracle, log_n):
     """ntt_roundtrip.rs:29-81 + exact forward values vs sezkp-ffts (config 2 at
-    2^20). 2^10..2^12 and 2^17..2^20 run the in-tile radix-16 (X16) pass."""
+    2^20). 2^10..2^12 and 2^17..2^20 run the in-tile radix-16 (X16) pass.
+    With a scratch buffer, without one (2^8..2^20: ntt_dif + the in-place bit
+    reversal; refused below 2^8) and with scratch == d; 2^5 (scratch copy),
+    2^9 (plain), 2^12 and 2^18 (X16), 2^19 (natural-store DIF) and 2^20
+    (radix-8) also on a non-default stream."""
     torch = gpu_ok
     n = 1 << log_n
     x = oracle.det_vec(n, 2024)
+    want = oracle.ntt_forward(x)
     d = _dev(torch, x)
     scratch = torch.empty_like(d)
     assert product.lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr(), log_n, 1, None) == 0
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(_host(d), oracle.ntt_forward(x))
+    np.testing.assert_array_equal(_host(d), want)
     assert product.lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr(), log_n, -1, None) == 0
     torch.cuda.synchronize()
     np.testing.assert_array_equal(_host(d), x)
+    _ntt_scratch_modes(torch, product, x, want, log_n, stream=log_n in (5, 9, 12, 18, 19, 20))
 
 
 @pytest.mark.parametrize("log_n", [21, 22, 23, 24, 25, 26])
 def test_ntt_large_matches_openmp_oracle(gpu_ok, product, oracle, log_n):
     """The headline LDE size (2^24) and config 4's 2^26 on one device: every
     output of sezkp_gl_ntt against the OpenMP oracle (ntt.rs:79-155), and the
-    inverse round trip."""
+    inverse round trip: with a scratch buffer (the natural-order DIT at
+    2^21..2^24, the transposed last pass at 2^25..2^26), without one and with
+    scratch == d (plain ntt_dif + bitrev_inplace: tile side 32 from 2^25);
+    2^22, 2^23 and 2^25 also on a non-default stream."""
     torch = gpu_ok
     oracle.use_mt(int(os.environ.get("OMP_NUM_THREADS", "8")))
     x = oracle.det_vec(1 << log_n, 2024 + log_n)
+    want = oracle.ntt_forward(x)
     d = _dev(torch, x)
     scratch = torch.empty_like(d)
     assert product.lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr(), log_n, 1, None) == 0
     torch.cuda.synchronize()
-    np.testing.assert_array_equal(_host(d), oracle.ntt_forward(x))
+    np.testing.assert_array_equal(_host(d), want)
     assert product.lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr(), log_n, -1, None) == 0
     torch.cuda.synchronize()
     np.testing.assert_array_equal(_host(d), x)
+    del d, scratch
+    _ntt_scratch_modes(torch, product, x, want, log_n, stream=log_n in (22, 23, 25))
+
+
+EPS = (1 << 32) - 1
+# canonical values at the carry / borrow boundaries of the 32-bit-lane arithmetic
+EDGE = np.array([0, 1, 2, P - 1, P - 2, EPS, EPS + 1, EPS - 1, 1 << 32, (1 << 32) + 1, 1 << 63, (1 << 63) - 1,
+                 P - EPS, P - EPS - 1, P - (1 << 32), (1 << 64) - (1 << 33), P >> 1, (P >> 1) + 1], dtype=np.uint64)
 
 
 @pytest.mark.parametrize("log_n", [4, 11, 12, 16, 20, 21, 24])
@@ -74,27 +129,92 @@ def test_ntt_edge_values_match_oracle(gpu_ok, product, oracle, log_n):
     p - eps, ...), drawn at random and as constant runs of p - 1, through
     every pass form (plain, X16, the 2^20 radix-8 passes, the natural-order
     DIT, the headline 2^24): forward values against the oracle, then the
-    inverse round trip."""
+    inverse round trip; with a scratch buffer, without one and with
+    scratch == d, 2^24 also on a non-default stream."""
     torch = gpu_ok
     if log_n > 20:
         oracle.use_mt(int(os.environ.get("OMP_NUM_THREADS", "8")))
     n = 1 << log_n
-    eps = (1 << 32) - 1
-    edge = np.array([0, 1, 2, P - 1, P - 2, eps, eps + 1, eps - 1, 1 << 32, (1 << 32) + 1, 1 << 63, (1 << 63) - 1,
-                     P - eps, P - eps - 1, P - (1 << 32), (1 << 64) - (1 << 33), P >> 1, (P >> 1) + 1], dtype=np.uint64)
     rng = np.random.default_rng(log_n)
-    x = edge[rng.integers(0, len(edge), n)]
+    x = EDGE[rng.integers(0, len(EDGE), n)]
     x[: n // 4] = P - 1
+    want = oracle.ntt_forward(x)
     d = _dev(torch, x)
     scratch = torch.empty_like(d)
     assert product.lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr(), log_n, 1, None) == 0
     torch.cuda.synchronize()
     got = _host(d)
     assert (got < P).all()
-    np.testing.assert_array_equal(got, oracle.ntt_forward(x))
+    np.testing.assert_array_equal(got, want)
     assert product.lib.sezkp_gl_ntt(d.data_ptr(), scratch.data_ptr(), log_n, -1, None) == 0
     torch.cuda.synchronize()
     np.testing.assert_array_equal(_host(d), x)
+    _ntt_scratch_modes(torch, product, x, want, log_n, stream=log_n == 24)
+
+
+@pytest.mark.parametrize("log_n", [27, 28])
+def test_ntt_2p27_2p28_no_scratch(gpu_ok, product, oracle, log_n):
+    """The two largest sizes the header accepts, in place without a scratch
+    buffer (ntt_dif as 8 + 7 + 12 / 8 + 8 + 12 stages, then the tile-side-32
+    bit reversal), with no CPU transform of that size:
+    sparse: 256 positions (0, 1, n/2, n - 1 and random ones) hold the edge
+    values; 2048 outputs (k = 0, 1, n/2, n - 1 and random k) must equal
+    sum_j v_j w_n^(j k mod n) in Python integers (w_n: the oracle's root), and
+    the inverse must return the input: a wrong permutation or pass plan moves
+    or changes sampled outputs;
+    dense: a canonical device-generated vector must come back exactly from
+    forward + inverse (arithmetic the sparse vector's zeros do not reach)."""
+    torch = gpu_ok
+    lib = product.lib
+    n = 1 << log_n
+    rng = np.random.default_rng(log_n)
+    pos = np.unique(np.concatenate([[0, 1, n // 2, n - 1], rng.integers(0, n, 252)]))
+    vals = EDGE[np.arange(len(pos)) % len(EDGE)]
+    vals[vals == 0] = P - 1  # every chosen position holds a non-zero value
+    d = torch.zeros(n, dtype=torch.int64, device="cuda")
+    d[torch.from_numpy(pos).cuda()] = torch.from_numpy(vals.view(np.int64)).cuda()
+    x0 = d.clone()
+    torch.cuda.synchronize()
+    assert lib.sezkp_gl_ntt(d.data_ptr(), None, log_n, 1, None) == 0
+    torch.cuda.synchronize()
+    ks = np.unique(np.concatenate([[0, 1, n // 2, n - 1], rng.integers(0, n, 2044)]))
+    got = _host(d[torch.from_numpy(ks).cuda()])
+    w = int(oracle.lib().orc_gl_root_2exp(log_n))
+    assert pow(w, n // 2, P) == P - 1  # a primitive n-th root
+    # w^e for e < n from two tables: w^e = hi[e >> 14] * lo[e & 16383]
+    lo = [1] * (1 << 14)
+    for i in range(1, 1 << 14):
+        lo[i] = lo[i - 1] * w % P
+    step = lo[-1] * w % P
+    hi = [1] * (n >> 14)
+    for i in range(1, n >> 14):
+        hi[i] = hi[i - 1] * step % P
+    pv = [(int(p), int(v)) for p, v in zip(pos, vals)]
+    for k, g in zip(ks, got):
+        k = int(k)
+        acc = 0
+        for j, v in pv:
+            e = j * k % n
+            acc += v * (hi[e >> 14] * lo[e & 16383] % P)
+        assert int(g) == acc % P, (log_n, k)
+    assert lib.sezkp_gl_ntt(d.data_ptr(), None, log_n, -1, None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(d, x0)
+    del x0
+    # dense: hi word <= 2^32 - 2 keeps every value below p
+    g = torch.Generator(device="cuda").manual_seed(log_n)
+    d.random_(0, 1 << 32, generator=g)
+    top = torch.empty_like(d).random_(0, (1 << 32) - 1, generator=g)
+    d |= top << 32
+    del top
+    x0 = d.clone()
+    torch.cuda.synchronize()
+    assert lib.sezkp_gl_ntt(d.data_ptr(), None, log_n, 1, None) == 0
+    torch.cuda.synchronize()
+    assert not torch.equal(d, x0)
+    assert lib.sezkp_gl_ntt(d.data_ptr(), None, log_n, -1, None) == 0
+    torch.cuda.synchronize()
+    assert torch.equal(d, x0)
 
 
 @pytest.mark.parametrize("vec", ["zeros", "delta", "ap"])
@@ -258,7 +378,9 @@ def test_prove_dictionary_branches_bit_exact(gpu_ok, product, oracle, monkeypatc
     is chosen per column on the device; force every branch at T = 2^17 in one
     block: head of tape 0 drifts by +1 per row (range 2^17 -> K = -1, computed
     leaves), full u16 symbols on tape 0 (R = 65536 -> K = 0), 16 symbols on
-    tape 1 (K = 2), {-1,0,1} moves (K = 3), all-zero tape 2 (R = 1 -> K = 4).
+    tape 1 (K = 1: at 2^17 rows level 2's 65536 entries cost more than they
+    save), 8 symbols on tape 2 (K = 2), {-1,0,1} moves (K = 3), tape 2 never
+    moves (R = 1 -> K = 4). dict_plans() must report exactly these levels.
     The same bytes must come out with the dictionary path disabled."""
     rng = np.random.default_rng(17)
     T, tau = 1 << 17, 3
@@ -267,14 +389,28 @@ def test_prove_dictionary_branches_bit_exact(gpu_ok, product, oracle, monkeypatc
     mv[:, 0] = 1
     mv[:, 1] = rng.integers(-1, 2, T, dtype=np.int8)
     hw = np.zeros((T, tau), np.uint8)
-    hw[:, :2] = 1
+    hw[:, :] = 1
     ws = np.zeros((T, tau), np.uint16)
     ws[:, 0] = rng.integers(0, 65536, T)
     ws[:, 1] = rng.integers(0, 16, T)
+    ws[:, 2] = rng.integers(0, 8, T)
     blocks = product.partition(imv, mv, hw, ws, T)
     mroot = blocks.manifest_root()
     want = oracle.prove_v1(blocks, mroot)
     assert product.StarkV1.prove(blocks, mroot).proof_bytes == want
+    # the levels the planner chose (no plan hook set), per (kind, tape):
+    # kinds 0 input_mv, 3 mv, 4 write flag, 5 wsym, 6 head
+    monkeypatch.delenv("SEZKP_TEST_DICT_PLAN_ROWS_LOG", raising=False)
+    ctx = product.ProverContext(0)
+    ctx.upload(blocks)
+    assert ctx.prove(mroot).proof_bytes == want
+    plans = {(p["kind"], p["tape"]): p for p in ctx.dict_plans()}
+    ctx.close()
+    assert {k: p["K"] for k, p in plans.items()} == {
+        (0, 0): 3, (3, 0): 4, (4, 0): 4, (5, 0): 0, (6, 0): -1, (3, 1): 3, (4, 1): 4, (5, 1): 1, (6, 1): 0,
+        (3, 2): 4, (4, 2): 4, (5, 2): 2, (6, 2): 4}
+    assert {p["K"] for p in plans.values()} >= {-1, 0, 2, 3, 4}
+    assert all(p["a"] == 0 and p["delta"] == 0 for p in plans.values())  # 2^17 rows: 64 rows per lane
     # smaller tables above level 0 (lower K per column; the A/B switch)
     for cap in ("16", "4096"):
         monkeypatch.setenv("SEZKP_DICT_TAB_CAP", cap)

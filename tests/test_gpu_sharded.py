@@ -37,6 +37,7 @@ def _worker(rank, world, port, T, b, tau, seed, q, zero_at=None):
         p2 = ctx.prove(root).proof_bytes
         calls = dict(ctx._coll.calls)
         calls["stats"] = ctx.comm_stats()
+        calls["plans"] = ctx.dict_plans()
         ctx.close()
         q.put((rank, hashlib.sha256(p1).hexdigest(), p1 == p2, calls))
     except Exception as e:
@@ -81,6 +82,28 @@ def test_sharded_proof_matches_oracle(gpu_ok, product, oracle, world, T, b, tau,
         assert {"col_chunk_roots", "d_values", "layer0_run_roots", "fri_rep_values", "fri_run_roots",
                 "proof_allreduce"} | ({"lde_alltoall"} if a2a else set()) == set(st), sorted(st)
         assert all(c["bytes"] > 0 and c["ms"] >= 0 for c in calls["stats"])
+
+
+def test_sharded_dict_forms_128_rows_per_lane(gpu_ok, product, oracle, monkeypatch):
+    """A sharded rank of config 5's kind: P = 2 at T = 2^17 with the planner
+    told 2^21 rows per device (SEZKP_TEST_DICT_PLAN_ROWS_LOG, inherited by the
+    spawned ranks), so every rank commits and opens its K >= 3 columns (moves,
+    flags) with 128 rows per lane (a = 1), rank 1 from row0 = 2^16, each in
+    two full 2^15-row workgroups; the K = 2 columns (16 symbols, delta heads)
+    keep 64. Every rank returns the oracle's bytes."""
+    monkeypatch.setenv("SEZKP_TEST_DICT_PLAN_ROWS_LOG", "21")
+    T, b, tau, seed = 1 << 17, 512, 3, 21
+    blocks = product.synthetic_blocks(T, b, tau, seed)
+    want = hashlib.sha256(oracle.prove_v1(blocks, blocks.manifest_root())).hexdigest()
+    for rank, digest, repeat_ok, calls in _run(2, T, b, tau, seed):
+        assert digest == want and repeat_ok, f"rank {rank}: {digest}"
+        plans = {(p["kind"], p["tape"]): p for p in calls["plans"]}
+        assert len(plans) == 1 + 4 * tau
+        for (kind, tape), p in plans.items():
+            form = (p["K"], p["a"], p["delta"])
+            # moves in {-1,0,1}: R = 3; flags: R = 2; 16 symbols; heads walk by {-1,0,1} over 512 rows
+            want_form = {0: (3, 1, 0), 3: (3, 1, 0), 4: (4, 1, 0), 5: (2, 0, 0), 6: (2, 0, 1)}[kind]
+            assert form == want_form, (rank, kind, tape, p)
 
 
 def test_sharded_zero_step_blocks_match_oracle(gpu_ok, product, oracle):

@@ -202,6 +202,18 @@ def test_kernel_abi_rejects_null_pointers_before_any_launch(product):
     assert lib.sezkp_blocks_decode_jsonl(b"{}", 2, None, buf, 64) == E
 
 
+def test_dict_plans_rejects_a_null_context(product):
+    """sezkp_ctx_dict_plans without a context is SEZKP_E_INVALID whatever the
+    other arguments (the null-output and negative-max cases need a context:
+    tests/test_gpu_dict_forms.py)."""
+    lib, E = product.lib, product._lib.SEZKP_E_INVALID
+    buf = (product._lib.DictPlanInfo * 4)()
+    assert lib.sezkp_ctx_dict_plans(None, buf, 4) == E
+    assert lib.sezkp_ctx_dict_plans(None, None, 0) == E
+    assert lib.sezkp_ctx_dict_plans(None, buf, -1) == E
+    assert C.sizeof(product._lib.DictPlanInfo) == 40  # sezkp_dict_plan_info: 8 x 32 bits + int64
+
+
 def test_block_shapes_checked_before_the_c_abi(product):
     """partial views (meta_only, concat_meta, with_steps)
     and wrong row counts must be refused on the host, since sezkp_block_view
