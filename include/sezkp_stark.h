@@ -190,6 +190,75 @@ typedef struct sezkp_dict_plan_info {
 } sezkp_dict_plan_info;
 int32_t sezkp_ctx_dict_plans(const sezkp_ctx* ctx, sezkp_dict_plan_info* out, int32_t max);
 
+/* ------------------------------------------------ full-trace AIR audit
+ * Does the committed trace satisfy the AIR, on every row? The reference
+ * verifier recomputes the composition (air.rs:49-136) only on its 30 opened
+ * rows (verify.rs:156-182), and there only bool_flag, mv_domain, head_update
+ * and the two boundary terms (air.rs:209-238): a bad row in a long trace is
+ * rarely queried, and the guarded range constraints (head, slack, symbol,
+ * air.rs:73-112) are checked by nobody. The audit looks at every (row, tape)
+ * cell of the columns the prover commits (openings.rs:182-273: h the
+ * block-local post-move head, m the move, f the write flag, s the symbol, w
+ * the window length, in_off / out_off the head offsets), as canonical
+ * Goldilocks values:
+ *   0 mv_domain    m (m - 1) (m + 1)                        (air.rs:67)
+ *   1 head_range   f (h - low16(h))                         (air.rs:75-85)
+ *   2 slack_range  f (slack - low16(slack)), slack = w-1-h  (air.rs:87-99)
+ *   3 sym_range    f (s - (s & 15))                         (air.rs:101-112)
+ *   4 boundary     is_first (h - m - in_off) + is_last (h - out_off)
+ *                                                           (air.rs:119-136)
+ * The two boundary terms are one family: the prover reuses one alpha for both
+ * (prover.rs:86-98); a boundary cell counts when either term is non-zero (on
+ * a one-row block they can cancel inside the cell, -1 + 1: violating, yet no
+ * verifier sees it), while the first-cell search takes their sum, the term as
+ * composed, so first_value is non-zero at a first cell and boundary can have
+ * cells > 0 with no first cell. bool_flag is identically zero (upload normalises the flag
+ * to 0/1) and so is head_update (h is the prefix sum of m inside a block and
+ * the constraint is masked on a block's last row): neither is a family.
+ * Per family: `cells` non-zero cells, `rows` rows holding one, the smallest
+ * such cell in (row, tape) order (first_row = UINT64_MAX when none) and the
+ * term there. Per trace two classes of rows, each with a count, a first row
+ * (UINT64_MAX when none) and an optional bitmap (row i = bit i % 8 of byte
+ * i / 8, bits from n_rows on are 0):
+ *   violating   some cell of some family is non-zero: the AIR fails here;
+ *   rejectable  the sum over the tapes (in the field) of term 0 or of term 4
+ *               is non-zero: the verifier's opened-row check fails when this
+ *               row is queried, whatever the transcript (up to a 2^-64
+ *               coincidence of the alphas). Cells can cancel across tapes
+ *               (m = +2 and -2: 6 - 6 = 0), so violating rows need not be
+ *               rejectable.
+ * Extends the reference, which has no counterpart. */
+#define SEZKP_AIR_FAMILIES 5   /* mv_domain, head_range, slack_range, sym_range, boundary */
+typedef struct sezkp_air_family {
+  uint64_t cells, rows, first_row;
+  uint32_t first_tape, pad;
+  uint64_t first_value;
+} sezkp_air_family;
+typedef struct sezkp_air_audit {
+  uint64_t n_rows;
+  uint32_t tau, pad;
+  uint64_t rows_violating, first_violating, rows_rejectable, first_rejectable;
+  sezkp_air_family fam[SEZKP_AIR_FAMILIES];
+} sezkp_air_audit;
+/* Audits the trace image the context's proofs read: that of the last upload,
+ * or of the last staged trace a prove has consumed. Runs the row expansion
+ * and the audit kernel on the context's stream and synchronises it.
+ * violating_bits / rejectable_bits: NULL, or host buffers of
+ * (n_rows + 7) / 8 bytes. The audit's device buffers (the bitmaps and a
+ * counter block) are allocated by the first audit of an upload's shape and
+ * kept for the next. SEZKP_E_INVALID: null ctx or out, no trace uploaded, a
+ * proof in flight, more than 256 tapes, a block whose head leaves the i32
+ * range (the message of prove; the context stays usable), a staged trace
+ * that no prove has consumed yet (prove first: the audit reads the image the
+ * proofs read), or a sharded context (it holds only its rank's rows; audit on
+ * a sezkp_ctx_create context). */
+int32_t sezkp_ctx_air_audit(sezkp_ctx* ctx, sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits,
+                            char* err, size_t err_len);
+/* Stateless: device 0, upload, audit. The bitmaps are library-allocated
+ * ((n_rows + 7) / 8 bytes, sezkp_buf_free) when the pointers are not NULL. */
+int32_t sezkp_stark_v1_air_audit(const sezkp_block_view* blocks, sezkp_air_audit* out, sezkp_buf* violating_bits,
+                                 sezkp_buf* rejectable_bits, char* err, size_t err_len);
+
 /* ------------------------------------------------ sharded proving (one proof, P GPUs)
  * One process per GPU; every rank uploads the same blocks and calls prove()
  * with the same manifest root; every rank returns the identical proof bytes.

@@ -4,6 +4,7 @@
 //   commit --blocks B(.cbor|.json|.jsonl|.ndjson) --out M
 //   verify-commit --blocks B --manifest M
 //   export-jsonl --input B(.cbor|.json|.jsonl|.ndjson) --output B.jsonl
+//   audit --blocks B(.cbor|.json|.jsonl|.ndjson) [--json]   (full-trace AIR audit; exit 3 when a row violates)
 // Semantics follow crates/sezkp-cli/src/main.rs:429-578 (manifest precheck,
 // .json/.cbor block files only for prove/verify, write_proof_auto by extension)
 // and crates/sezkp-merkle/src/lib.rs:259-337 (commit / precheck).
@@ -100,7 +101,7 @@ std::string pretty_artifact(const Artifact& a) {
 
 struct Args {
   std::string cmd, backend = "stark", blocks, manifest, out, proof, input;
-  bool stream = false, assume = false;
+  bool stream = false, assume = false, json = false;
   std::string t = "32", b = "4", tau = "2";  // simulate defaults (main.rs:87-100)
 };
 
@@ -345,6 +346,58 @@ int cmd_simulate(const Args& a) {
   return 0;
 }
 
+// `audit`: the full-trace AIR audit (sezkp_stark_v1_air_audit; no counterpart
+// in the reference CLI). Exit 0 when the AIR holds on every row, 3 when a row
+// violates it.
+int cmd_audit(const Args& a) {
+  if (a.blocks.empty()) { fprintf(stderr, "Error: audit needs --blocks\n"); return 2; }
+  std::string err;
+  BlockStore bs;
+  if (!load_blocks_any(a.blocks, bs, err)) { fprintf(stderr, "Error: read blocks %s: %s\n", a.blocks.c_str(), err.c_str()); return 1; }
+  sezkp_air_audit au;
+  char msg[512] = {0};
+  if (sezkp_stark_v1_air_audit(&bs.view, &au, nullptr, nullptr, msg, sizeof msg)) {
+    fprintf(stderr, "Error: AIR audit failed: %s\n", msg);
+    return 1;
+  }
+  static const char* NAME[SEZKP_AIR_FAMILIES] = {"mv_domain", "head_range", "slack_range", "sym_range", "boundary"};
+  // NUM_QUERIES = 30 independent draws mod n (params.rs:31,95-105)
+  double miss = 1.0;
+  for (int q = 0; q < 30; q++) miss *= 1.0 - (double)au.rows_rejectable / (double)au.n_rows;
+  const double p_reject = 1.0 - miss;
+  auto row = [](uint64_t r) { return r == UINT64_MAX ? std::string("null") : std::to_string(r); };
+  if (a.json) {
+    printf("{\"n_rows\": %llu, \"tau\": %u, \"ok\": %s, \"families\": {", (unsigned long long)au.n_rows, au.tau,
+           au.rows_violating ? "false" : "true");
+    for (int f = 0; f < SEZKP_AIR_FAMILIES; f++) {
+      const sezkp_air_family& m = au.fam[f];
+      printf("%s\"%s\": {\"cells\": %llu, \"rows\": %llu, \"first_row\": %s, \"first_tape\": %u, \"first_value\": %llu}",
+             f ? ", " : "", NAME[f], (unsigned long long)m.cells, (unsigned long long)m.rows, row(m.first_row).c_str(),
+             m.first_tape, (unsigned long long)m.first_value);
+    }
+    printf("}, \"rows_violating\": %llu, \"first_violating\": %s, \"rows_rejectable\": %llu, \"first_rejectable\": %s, "
+           "\"verify_reject_probability\": %.17g}\n",
+           (unsigned long long)au.rows_violating, row(au.first_violating).c_str(),
+           (unsigned long long)au.rows_rejectable, row(au.first_rejectable).c_str(), p_reject);
+  } else {
+    printf("AIR audit: %llu rows, tau=%u\n", (unsigned long long)au.n_rows, au.tau);
+    for (int f = 0; f < SEZKP_AIR_FAMILIES; f++) {
+      const sezkp_air_family& m = au.fam[f];
+      if (m.cells)
+        printf("%-12s cells=%llu rows=%llu first: row %llu tape %u value %llu\n", NAME[f], (unsigned long long)m.cells,
+               (unsigned long long)m.rows, (unsigned long long)m.first_row, m.first_tape,
+               (unsigned long long)m.first_value);
+      else
+        printf("%-12s cells=0 rows=0\n", NAME[f]);
+    }
+    printf("violating rows:  %llu (first %s)\n", (unsigned long long)au.rows_violating, row(au.first_violating).c_str());
+    printf("rejectable rows: %llu (first %s)\n", (unsigned long long)au.rows_rejectable,
+           row(au.first_rejectable).c_str());
+    printf("verifier rejects with probability %.6g (30 queries)\n", p_reject);
+  }
+  return au.rows_violating ? 3 : 0;
+}
+
 void usage() {
   fprintf(stderr,
           "usage: sezkp-cli prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]\n"
@@ -352,7 +405,8 @@ void usage() {
           "       sezkp-cli commit --blocks B --out M\n"
           "       sezkp-cli verify-commit --blocks B --manifest M\n"
           "       sezkp-cli export-jsonl --input B --output B.jsonl\n"
-          "       sezkp-cli simulate --t T --b STEPS_PER_BLOCK --tau TAU --out-blocks B(.cbor|.jsonl)\n");
+          "       sezkp-cli simulate --t T --b STEPS_PER_BLOCK --tau TAU --out-blocks B(.cbor|.jsonl)\n"
+          "       sezkp-cli audit --blocks B [--json]\n");
 }
 
 }  // namespace
@@ -379,6 +433,7 @@ int main(int argc, char** argv) {
     else if (s == "--tau") val(a.tau);
     else if (s == "--stream") a.stream = true;
     else if (s == "--assume-committed") a.assume = true;
+    else if (s == "--json") a.json = true;
     else { fprintf(stderr, "unknown argument %s\n", s.c_str()); usage(); return 2; }
   }
   for (auto& c : a.backend) c = (char)tolower((unsigned char)c);
@@ -386,6 +441,7 @@ int main(int argc, char** argv) {
   if (a.cmd == "simulate") return cmd_simulate(a);
   if (a.cmd == "verify-commit") return cmd_verify_commit(a);
   if (a.cmd == "export-jsonl") return cmd_export_jsonl(a);
+  if (a.cmd == "audit") return cmd_audit(a);
   if (a.backend != "stark") {
     fprintf(stderr, "Error: only --backend stark is implemented by the MI355X build\n");
     return 2;

@@ -313,6 +313,18 @@ struct sezkp_ctx {
   // test hook (SEZKP_DEBUG_STALL_AFTER): a mapped word the stream waits on
   // after a collective, so that the collective looks stuck; set at destroy
   uint32_t* stall_word = nullptr;
+  // AIR audit (sezkp_ctx_air_audit): the counter block (AUD_WORDS), then the
+  // violating and the rejectable bitmap of (n + 63) / 64 words each. Allocated
+  // by the first audit and kept while uploads keep n: outside the workspace,
+  // so upload and prove allocate what they do without it.
+  uint64_t* d_audit = nullptr;
+  uint64_t* h_audit = nullptr;  // pinned: the counter block's landing place
+  uint64_t audit_n = 0;
+  void free_audit() {
+    if (d_audit) (void)hipFree(d_audit);
+    d_audit = nullptr;
+    audit_n = 0;
+  }
 
   static void* take_spare(std::multimap<size_t, void*>& m, size_t bytes) {
     auto it = m.find(bytes);
@@ -438,6 +450,8 @@ struct sezkp_ctx {
     if (stc) (void)hipStreamSynchronize(stc);
     free_all();
     release_spares();
+    free_audit();
+    if (h_audit) (void)hipHostFree(h_audit);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : coll_ev) (void)hipEventDestroy(e);
@@ -479,6 +493,8 @@ struct sezkp_ctx {
   // the prover with the host transcript (three round trips: column roots,
   // layer-0 root, FRI roots)
   size_t prove_body(const uint8_t root[32]);
+  // full-trace AIR audit of the active trace image (bitmaps: null or (n + 7) / 8 host bytes)
+  void air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits);
 };
 
 // SEZKP_COLL_TIMEOUT_S: how long a sharded rank waits for a stream holding
@@ -623,6 +639,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     throw Err{SEZKP_E_INVALID, "n_base must be a power of two (got " + std::to_string(rows) + ")"};  // lde.rs:51
   if (rows > (1ULL << 28)) throw Err{SEZKP_E_INVALID, "trace too long for one device (n > 2^28)"};
   n = rows;
+  if (audit_n != n) free_audit();
   logn = ilog2(n);
   logN = logn + BLOWUP_LOG2;
   N = 1ULL << logN;
@@ -1122,6 +1139,80 @@ void sezkp_ctx::take_staged() {
   }
 }
 
+static std::string head_range_msg(const std::string& who) {
+  return "a block's head position leaves the i32 range" + who +
+         " (block too long for its moves: block length x max |mv| must stay below 2^31)";
+}
+
+// Full-trace AIR audit (sezkp_stark.h; semantics at k_air_audit, trace.hip):
+// air.rs:49-136 on every (row, tape) cell, and the rows the verifier's
+// opened-row check (verify.rs:156-182) would reject, with the alpha reuse of
+// prover.rs:86-98 (one boundary family). The derived columns (row -> block,
+// first / last flags, heads) are written by prove's k_expand, so the audit
+// runs launch_expand itself: it works before the first prove of an upload.
+void sezkp_ctx::air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits) {
+  if (sharded())
+    throw Err{SEZKP_E_INVALID, "air_audit: a sharded context holds only its rank's rows (audit on a single-device "
+                               "context)"};
+  if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded"};
+  if (broken) throw Err{SEZKP_E_DEVICE, "context unusable: an earlier call could not clear a tripped guard word"};
+  {
+    std::lock_guard<std::mutex> lk(stage_mu);
+    if (staged)
+      throw Err{SEZKP_E_INVALID, "air_audit: a staged trace is pending (prove first: the audit reads the image the "
+                                 "proofs read)"};
+  }
+  if (tau > 256) throw Err{SEZKP_E_INVALID, "air_audit takes at most 256 tapes"};
+  HIP_OR_THROW(hipSetDevice(device));
+  const size_t words = (size_t)((n + 63) / 64), bytes = (size_t)((n + 7) / 8);
+  if (!h_audit) HIP_OR_THROW(hipHostMalloc(&h_audit, (size_t)AUD_WORDS * 8, hipHostMallocDefault));
+  if (!d_audit) {
+    HIP_OR_THROW(hipMalloc(&d_audit, ((size_t)AUD_WORDS + 2 * words) * 8));
+    audit_n = n;
+  }
+  const AirAuditOut O{d_audit, d_audit + AUD_WORDS, d_audit + AUD_WORDS + words};
+  HIP_OR_THROW(launch_expand(st, T, 0, nblk, d_err));
+  HIP_OR_THROW(launch_air_audit(st, T, O, d_err));
+  // the counters and the guard word (k_air_audit_first put it beside them): one copy
+  const uint64_t* c = h_audit;
+  HIP_OR_THROW(hipMemcpyAsync(h_audit, d_audit, (size_t)AUD_WORDS * 8, hipMemcpyDeviceToHost, st));
+  HIP_OR_THROW(hipStreamSynchronize(st));
+  const uint32_t guard = (uint32_t)c[AUD_GUARD];
+  if (guard) {
+    // as prove's check_guards: clear the data-dependent flag, stream-ordered,
+    // so that a later prove of a good trace on this context succeeds
+    hipError_t me = hipMemsetAsync(d_err, 0, 64, st);
+    if (me == hipSuccess) me = hipStreamSynchronize(st);
+    if (me != hipSuccess) {
+      broken = true;
+      throw Err{SEZKP_E_DEVICE, std::string("guard word tripped (code ") + std::to_string(guard) +
+                                    ") and clearing it failed: " + hipGetErrorString(me) + "; the context is unusable"};
+    }
+    const std::string who = " on rank " + std::to_string(rank);
+    if (guard & GUARD_HEAD_RANGE) throw Err{SEZKP_E_INVALID, head_range_msg(who)};
+    throw Err{SEZKP_E_DEVICE, "guard word tripped" + who + " (code " + std::to_string(guard) + ")"};
+  }
+  if (violating_bits) HIP_OR_THROW(hipMemcpyAsync(violating_bits, O.viol, bytes, hipMemcpyDeviceToHost, st));
+  if (rejectable_bits) HIP_OR_THROW(hipMemcpyAsync(rejectable_bits, O.rej, bytes, hipMemcpyDeviceToHost, st));
+  if (violating_bits || rejectable_bits) HIP_OR_THROW(hipStreamSynchronize(st));
+  *out = sezkp_air_audit{};
+  out->n_rows = n;
+  out->tau = tau;
+  out->rows_violating = c[AUD_NVIOL];
+  out->first_violating = c[AUD_FVIOL];
+  out->rows_rejectable = c[AUD_NREJ];
+  out->first_rejectable = c[AUD_FREJ];
+  for (int f = 0; f < AIR_FAMILIES; f++) {
+    sezkp_air_family& a = out->fam[f];
+    const uint64_t key = c[AUD_KEY + f];
+    a.cells = c[AUD_CELLS + f];
+    a.rows = c[AUD_ROWS + f];
+    a.first_row = key == ~0ull ? ~0ull : key >> 8;
+    a.first_tape = key == ~0ull ? 0 : (uint32_t)(key & 0xFF);
+    a.first_value = c[AUD_VALUE + f];
+  }
+}
+
 size_t sezkp_ctx::prove(const uint8_t mroot[32]) {
   if (broken)
     throw Err{SEZKP_E_DEVICE, "context unusable: an earlier prove aborted the communicator after a failure past "
@@ -1288,9 +1379,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
         }
       }
       const std::string who = " on rank " + std::to_string(sharded ? r : rank);
-      if (g & GUARD_HEAD_RANGE)
-        throw Err{SEZKP_E_INVALID, "a block's head position leaves the i32 range" + who +
-                                       " (block too long for its moves: block length x max |mv| must stay below 2^31)"};
+      if (g & GUARD_HEAD_RANGE) throw Err{SEZKP_E_INVALID, head_range_msg(who)};
       if (g) throw Err{SEZKP_E_DEVICE, "column commitment guard tripped" + who + " (code " + std::to_string(g) + ")"};
     }
   };
@@ -2047,6 +2136,22 @@ int32_t sezkp_ctx_prove(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_
   }
 }
 
+int32_t sezkp_ctx_air_audit(sezkp_ctx* ctx, sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits,
+                            char* err, size_t err_len) {
+  try {
+    if (!ctx || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    ctx->air_audit(out, violating_bits, rejectable_bits);
+    return SEZKP_OK;
+  } catch (const Err& e) {
+    set_err(err, err_len, e.msg);
+    return e.code;
+  } catch (const std::exception& e) {
+    set_err(err, err_len, e.what());
+    return SEZKP_E_NOMEM;
+  }
+}
+
 int32_t sezkp_ctx_prove_borrow(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, const uint8_t** data,
                                size_t* len, char* err, size_t err_len) {
   (void)flags;
@@ -2249,6 +2354,34 @@ int32_t sezkp_stark_v1_prove(const sezkp_block_view* blocks, const uint8_t manif
     } catch (const Err& e) {
       set_err(err, err_len, e.msg);
       rc = e.code;
+    }
+  }
+  sezkp_ctx_destroy(ctx);
+  return rc;
+}
+
+int32_t sezkp_stark_v1_air_audit(const sezkp_block_view* blocks, sezkp_air_audit* out, sezkp_buf* violating_bits,
+                                 sezkp_buf* rejectable_bits, char* err, size_t err_len) {
+  if (!blocks || !out) {  // before any device is touched
+    set_err(err, err_len, "null argument");
+    return SEZKP_E_INVALID;
+  }
+  sezkp_ctx* ctx = sezkp_ctx_create(0, err, err_len);
+  if (!ctx) return SEZKP_E_DEVICE;
+  int32_t rc = sezkp_ctx_upload(ctx, blocks, err, err_len);
+  if (rc == SEZKP_OK) {
+    const size_t bytes = (size_t)((ctx->n + 7) / 8);
+    std::vector<uint8_t> vb(violating_bits ? bytes : 0), rb(rejectable_bits ? bytes : 0);
+    rc = sezkp_ctx_air_audit(ctx, out, violating_bits ? vb.data() : nullptr, rejectable_bits ? rb.data() : nullptr,
+                             err, err_len);
+    if (rc == SEZKP_OK) {
+      try {
+        if (violating_bits) to_buf(vb, violating_bits);
+        if (rejectable_bits) to_buf(rb, rejectable_bits);
+      } catch (const Err& e) {
+        set_err(err, err_len, e.msg);
+        rc = e.code;
+      }
     }
   }
   sezkp_ctx_destroy(ctx);

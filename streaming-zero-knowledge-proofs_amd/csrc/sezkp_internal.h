@@ -168,6 +168,37 @@ struct ComposeTerms {
   const uint32_t* row_blk;    // = TraceDev::row_blk
 };
 
+// Full-trace AIR audit (k_air_audit): per constraint family the non-zero
+// (row, tape) cells, and the rows a verifier query would reject. Families in
+// the order of SEZKP_AIR_FAMILIES (sezkp_stark.h): mv_domain, head_range,
+// slack_range, sym_range, boundary. `cnt` is AUD_WORDS u64 words: the sums
+// [0, AUD_KEY), the minima [AUD_KEY, AUD_VALUE) (all ones = none; k_air_audit
+// keeps them complemented, as maxima over a block zeroed by one memset, and
+// k_air_audit_first turns them over), the term at each family's first cell,
+// and a copy of the guard word; viol / rej are bitmaps of (n + 63) / 64 words,
+// row i = bit i % 64 of word i / 64.
+constexpr int AIR_FAMILIES = 5;
+enum AuditWord {
+  AUD_CELLS = 0,                  // [5] non-zero cells per family
+  AUD_ROWS = AIR_FAMILIES,        // [5] rows with a non-zero cell per family
+  AUD_NVIOL = 2 * AIR_FAMILIES,   // violating rows
+  AUD_NREJ,                       // rejectable rows
+  AUD_KEY,                        // [5] smallest (row << 8) | tape per family
+  AUD_FVIOL = AUD_KEY + AIR_FAMILIES,  // first violating row
+  AUD_FREJ,                       // first rejectable row
+  AUD_VALUE,                      // [5] canonical term at the first cell
+  AUD_GUARD = AUD_VALUE + AIR_FAMILIES,  // the guard word after the audit's k_expand
+  AUD_WORDS
+};
+struct AirAuditOut {
+  uint64_t* cnt;
+  uint64_t* viol;
+  uint64_t* rej;
+};
+// needs the derived columns of launch_expand on the same stream; tau <= 256;
+// d_err: the guard word copied to cnt[AUD_GUARD]
+hipError_t launch_air_audit(hipStream_t st, const TraceDev& T, const AirAuditOut& O, const uint32_t* d_err);
+
 // guard word bits (d_err): a kernel saw input it cannot represent
 constexpr uint32_t GUARD_HEAD_RANGE = 0x100u;  // k_expand: a head outside i32
 

@@ -704,6 +704,273 @@ __global__ void __launch_bounds__(TR_THREADS) k_compose_combine(ComposeTerms Tm,
   out[i] = compose_value(Tm, K, i, x);
 }
 
+// ------------------------------------------------------------ AIR audit
+// Which (row, tape) cells of the committed trace break which constraint of
+// compose_row / compose_boundary (air.rs:49-136), over all n rows: the
+// reference verifier recomputes the AIR only on its 30 opened rows
+// (verify.rs:156-182), and not the range constraints at all. Five families
+// (AUD_* order): mv_domain m(m-1)(m+1) (air.rs:67), head_range
+// f (h - low16(h)) (:75-85), slack_range f (slack - low16(slack)) with
+// slack = w - 1 - h (:87-99), sym_range f (s - (s & 15)) (:101-112) and
+// boundary is_first (h - m - in_off) + is_last (h - out_off) (:119-136; one
+// family: the prover gives both the same alpha, prover.rs:86-98). Terms are
+// canonical field values of the committed columns (h: the block-local
+// post-move head of k_expand). bool_flag is identically zero (the image holds
+// 0/1 flags) and so is head_update (head is the prefix sum of mv inside a
+// block, and the constraint is masked on a block's last row): neither is
+// audited. ComposeTerms cannot serve: it keeps per-row sums over the tapes,
+// where cells cancel (mv = +2 and -2 on two tapes: 6 - 6 = 0).
+// A boundary cell counts (cells, rows, violating) when either of its two
+// terms is non-zero: on a one-row block they can cancel inside one cell
+// (-1 + 1); the first-cell search takes the sum, the term as composed, so
+// first_value is never 0 at a first cell.
+// A row is `violating` when any cell of any family is non-zero, and
+// `rejectable` when the verifier's opened-row check (air.rs:209-238: mv_domain
+// and the boundary terms, summed over the tapes in the field) is non-zero for
+// generic alphas.
+// RW adjacent rows per lane (2; 1 when n = 1; 1 or 4 on request),
+// a loop over the tapes: the lane's mv / wflag / wsym / head cells of one tape
+// are single loads, as in k_compose_terms. A wave's 64 RW rows are RW words of
+// each bitmap, put together from one __ballot per row slot (lane l < RW
+// spreads the ballots' bits of its 64 / RW lanes to every RW-th position); row counts are
+// __popcll of the ballots; n < 64 leaves the single word partial. Counts and
+// first cells (smallest key (row << 8) | tape) stay in registers over the
+// workgroup's grid-stride loop, then wave shuffles, LDS, and one 64-bit
+// integer atomic per non-trivial counter per workgroup: the result does not
+// depend on scheduling. The minima are kept complemented (atomicMax), so one
+// memset of zeros clears the counter block. k_air_audit_first turns them
+// over and recomputes the term at each family's first cell.
+__device__ __forceinline__ void audit_terms(const TraceDev& T, int r, uint32_t blk, bool is_first, bool is_last,
+                                            int32_t m, uint32_t wf, uint32_t sym, int32_t head, int32_t& c2,
+                                            uint64_t (&t)[AIR_FAMILIES], bool& bd_any) {
+  const uint64_t hf = gl_from_i64(head);
+  c2 = m * m * m - m;
+  t[0] = gl_from_i64(c2);
+  t[1] = t[2] = t[3] = 0;
+  if (wf) {
+    t[1] = hf & ~0xFFFFULL;
+    const uint64_t winlen = T.blk_winlen[(uint64_t)r * T.nblk + blk];
+    t[2] = gl_sub(gl_sub(winlen, 1), hf) & ~0xFFFFULL;
+    t[3] = (uint64_t)(sym & ~0xFu);
+  }
+  const uint64_t bf = is_first ? gl_sub(gl_sub(hf, gl_from_i64(m)), T.blk_offin[(uint64_t)r * T.nblk + blk]) : 0;
+  const uint64_t bl = is_last ? gl_sub(hf, T.blk_offout[(uint64_t)r * T.nblk + blk]) : 0;
+  t[4] = gl_add(bf, bl);
+  bd_any = (bf | bl) != 0;
+}
+
+// grid-stride beyond: at most this many workgroups' atomics on the counter
+// block (T = 2^21, tau = 8, the audit call's device span: 0.168 / 0.153 /
+// 0.151 / 0.201 ms at 2048 / 1024 / 512 / 256 workgroups, 4 rows per lane)
+constexpr int AUD_MAX_WGS = 1024;
+// 2 rows per lane: k_air_audit 92 us against 107 (4 rows: 165 VGPRs, 3 waves per SIMD) and 116 (1 row) at
+// T = 2^21, tau = 8 (profiles/air_audit/kernel_stats.txt)
+constexpr int AUD_ROWS_PER_LANE = 2;
+
+// the low 64 / RW bits of x, bit k moved to position RW k
+template <int RW>
+__device__ __forceinline__ uint64_t audit_spread(uint64_t x) {
+  if constexpr (RW == 4) {
+    x &= 0xFFFFull;
+    x = (x | (x << 24)) & 0x000000FF000000FFull;
+    x = (x | (x << 12)) & 0x000F000F000F000Full;
+    x = (x | (x << 6)) & 0x0303030303030303ull;
+    x = (x | (x << 3)) & 0x1111111111111111ull;
+  } else if constexpr (RW == 2) {
+    x &= 0xFFFFFFFFull;
+    x = (x | (x << 16)) & 0x0000FFFF0000FFFFull;
+    x = (x | (x << 8)) & 0x00FF00FF00FF00FFull;
+    x = (x | (x << 4)) & 0x0F0F0F0F0F0F0F0Full;
+    x = (x | (x << 2)) & 0x3333333333333333ull;
+    x = (x | (x << 1)) & 0x5555555555555555ull;
+  }
+  return x;
+}
+
+template <int RW>
+__global__ void __launch_bounds__(TR_THREADS) k_air_audit(TraceDev T, AirAuditOut O) {
+  static_assert(RW == 1 || RW == 2 || RW == 4, "1, 2 or 4 rows per lane");
+  using Narrow = typename std::conditional<RW == 1, uint8_t,
+                                           typename std::conditional<RW == 2, uint16_t, uint32_t>::type>::type;
+  using Wide = typename std::conditional<RW == 1, uint16_t,
+                                         typename std::conditional<RW == 2, uint32_t, uint64_t>::type>::type;
+  // sums [0, AUD_KEY), complemented minima [AUD_KEY, AUD_VALUE)
+  __shared__ unsigned long long sh[AUD_VALUE];
+  const int tid = threadIdx.x, lane = tid & 63;
+  if (tid < AUD_VALUE) sh[tid] = 0ull;
+  __syncthreads();
+  const uint64_t n = T.n;  // a multiple of RW
+  uint32_t cells[AIR_FAMILIES], rows[AIR_FAMILIES];
+  uint64_t key[AIR_FAMILIES];
+#pragma unroll
+  for (int f = 0; f < AIR_FAMILIES; f++) {
+    cells[f] = rows[f] = 0;
+    key[f] = ~0ull;
+  }
+  uint64_t n_viol = 0, n_rej = 0, f_viol = ~0ull, f_rej = ~0ull;  // wave-uniform
+  constexpr uint64_t WG_ROWS = (uint64_t)TR_THREADS * RW;
+  for (uint64_t base = (uint64_t)blockIdx.x * WG_ROWS; base < n; base += (uint64_t)gridDim.x * WG_ROWS) {
+    const uint64_t i = base + (uint64_t)RW * tid;
+    uint32_t violm = 0, rejm = 0;  // bit j: row i + j
+    if (i < n) {
+      const Narrow flw = *reinterpret_cast<const Narrow*>(T.row_flags + i);
+      uint32_t blk[RW];
+      if constexpr (RW == 1) {
+        blk[0] = T.row_blk[i];
+      } else {
+#pragma unroll
+        for (int j = 0; j < RW; j += 2) {
+          const uint2 b2 = *reinterpret_cast<const uint2*>(T.row_blk + i + j);
+          blk[j] = b2.x;
+          blk[j + 1] = b2.y;
+        }
+      }
+      int64_t s_c2[RW];
+      uint64_t s_bd[RW];
+      uint32_t hit[RW];
+#pragma unroll
+      for (int j = 0; j < RW; j++) {
+        s_c2[j] = 0;
+        s_bd[j] = 0;
+        hit[j] = 0;
+      }
+      for (int r = 0; r < T.tau; r++) {
+        const uint64_t o = (uint64_t)r * n + i;
+        const Narrow mvw = *reinterpret_cast<const Narrow*>(T.mv + o);
+        const Narrow wfw = *reinterpret_cast<const Narrow*>(T.wflag + o);
+        const Wide wsw = *reinterpret_cast<const Wide*>(T.wsym + o);
+        int32_t head[RW];
+        if constexpr (RW == 1) {
+          head[0] = T.head[o];
+        } else {
+#pragma unroll
+          for (int j = 0; j < RW; j += 2) {
+            const int2 h2 = *reinterpret_cast<const int2*>(T.head + o + j);
+            head[j] = h2.x;
+            head[j + 1] = h2.y;
+          }
+        }
+#pragma unroll
+        for (int j = 0; j < RW; j++) {
+          int32_t c2;
+          uint64_t t[AIR_FAMILIES];
+          bool bd_any;
+          audit_terms(T, r, blk[j], (flw >> (8 * j)) & 1, (flw >> (8 * j + 1)) & 1, (int8_t)((mvw >> (8 * j)) & 0xFF),
+                      (uint32_t)((wfw >> (8 * j)) & 0xFF), (uint32_t)((wsw >> (16 * j)) & 0xFFFF), head[j], c2, t,
+                      bd_any);
+#pragma unroll
+          for (int f = 0; f < AIR_FAMILIES; f++) {
+            // a boundary cell counts when either of its two terms is non-zero;
+            // its first cell is the first whose sum (the composed term) is
+            if (f == 4 ? bd_any : t[f] != 0) {
+              cells[f]++;
+              hit[j] |= 1u << f;
+            }
+            const uint64_t k = ((i + j) << 8) | (uint64_t)r;
+            if (t[f] && k < key[f]) key[f] = k;  // (tapes of row i + 1 come before the later tapes of row i)
+          }
+          s_c2[j] += c2;  // |sum| < p: zero in the field iff zero
+          s_bd[j] = gl_add(s_bd[j], t[4]);
+        }
+      }
+#pragma unroll
+      for (int j = 0; j < RW; j++) {
+#pragma unroll
+        for (int f = 0; f < AIR_FAMILIES; f++) rows[f] += (hit[j] >> f) & 1;
+        violm |= (hit[j] != 0 ? 1u : 0u) << j;
+        rejm |= ((s_c2[j] != 0 || s_bd[j] != 0) ? 1u : 0u) << j;
+      }
+    }
+    // the wave's rows [wb, wb + 64 RW): lane l of ballot j is row wb + RW l + j
+    const uint64_t wb = base + (uint64_t)RW * (tid & ~63);
+    uint64_t wv = 0, wr = 0;
+#pragma unroll
+    for (int j = 0; j < RW; j++) {
+      const uint64_t bv = __ballot((violm >> j) & 1), br = __ballot((rejm >> j) & 1);
+      if (lane < RW) {
+        wv |= audit_spread<RW>(bv >> (lane * (64 / RW))) << j;
+        wr |= audit_spread<RW>(br >> (lane * (64 / RW))) << j;
+      }
+      if (bv) {
+        n_viol += (uint64_t)__popcll(bv);
+        f_viol = min(f_viol, wb + (uint64_t)RW * (uint64_t)__builtin_ctzll(bv) + j);
+      }
+      if (br) {
+        n_rej += (uint64_t)__popcll(br);
+        f_rej = min(f_rej, wb + (uint64_t)RW * (uint64_t)__builtin_ctzll(br) + j);
+      }
+    }
+    if (lane < RW && wb + 64 * (uint64_t)lane < n) {  // word l of the wave: rows wb + 64 l ...
+      O.viol[(wb >> 6) + lane] = wv;
+      O.rej[(wb >> 6) + lane] = wr;
+    }
+  }
+#pragma unroll
+  for (int f = 0; f < AIR_FAMILIES; f++) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      cells[f] += __shfl_xor(cells[f], o, 64);
+      rows[f] += __shfl_xor(rows[f], o, 64);
+      key[f] = min(key[f], __shfl_xor(key[f], o, 64));
+    }
+  }
+  if (lane == 0) {
+#pragma unroll
+    for (int f = 0; f < AIR_FAMILIES; f++) {
+      if (cells[f]) atomicAdd(&sh[AUD_CELLS + f], (unsigned long long)cells[f]);
+      if (rows[f]) atomicAdd(&sh[AUD_ROWS + f], (unsigned long long)rows[f]);
+      if (key[f] != ~0ull) atomicMax(&sh[AUD_KEY + f], (unsigned long long)~key[f]);
+    }
+    if (n_viol) {
+      atomicAdd(&sh[AUD_NVIOL], (unsigned long long)n_viol);
+      atomicMax(&sh[AUD_FVIOL], (unsigned long long)~f_viol);
+    }
+    if (n_rej) {
+      atomicAdd(&sh[AUD_NREJ], (unsigned long long)n_rej);
+      atomicMax(&sh[AUD_FREJ], (unsigned long long)~f_rej);
+    }
+  }
+  __syncthreads();
+  if (tid < AUD_VALUE) {
+    const unsigned long long v = sh[tid];
+    unsigned long long* dst = reinterpret_cast<unsigned long long*>(O.cnt) + tid;
+    if (v) {
+      if (tid < AUD_KEY) atomicAdd(dst, v);
+      // the word only grows: a stale read can at most let a needless atomic through
+      else if (__atomic_load_n(dst, __ATOMIC_RELAXED) < v) atomicMax(dst, v);
+    }
+  }
+}
+
+// One workgroup, after k_air_audit: the minima turned over (complemented
+// maxima -> all ones = none), the canonical term at each family's first cell
+// (0 when none) and the guard word beside the counters, so that one copy
+// brings the host everything.
+__global__ void __launch_bounds__(64) k_air_audit_first(TraceDev T, AirAuditOut O, const uint32_t* __restrict__ err) {
+  const int f = threadIdx.x;
+  if (f == AIR_FAMILIES) O.cnt[AUD_FVIOL] = ~O.cnt[AUD_FVIOL];
+  if (f == AIR_FAMILIES + 1) O.cnt[AUD_FREJ] = ~O.cnt[AUD_FREJ];
+  if (f == AIR_FAMILIES + 2) O.cnt[AUD_GUARD] = err ? (uint64_t)*err : 0;
+  if (f >= AIR_FAMILIES) return;
+  const uint64_t key = ~O.cnt[AUD_KEY + f];
+  uint64_t v = 0;
+  if (key != ~0ull && (key >> 8) < T.n && (int)(key & 0xFF) < T.tau) {
+    const uint64_t i = key >> 8;
+    const int r = (int)(key & 0xFF);
+    const uint64_t o = (uint64_t)r * T.n + i;
+    const uint32_t fl = T.row_flags[i];
+    int32_t c2;
+    uint64_t t[AIR_FAMILIES];
+    bool bd_any;
+    audit_terms(T, r, T.row_blk[i], fl & 1, (fl >> 1) & 1, T.mv[o], T.wflag[o], T.wsym[o], T.head[o], c2, t, bd_any);
+#pragma unroll
+    for (int g = 0; g < AIR_FAMILIES; g++)
+      if (g == f) v = t[g];
+  }
+  O.cnt[AUD_KEY + f] = key;
+  O.cnt[AUD_VALUE + f] = v;
+}
+
 // ------------------------------------------------ dictionary commitments
 // Exact memoization for the dense columns (input_mv, mv, write_flag,
 // write_sym, head). Their raw integers lie in a small range [min, min+R) on
@@ -1709,6 +1976,27 @@ hipError_t launch_compose_combine(hipStream_t st, const ComposeTerms& Tm, const 
   if (grid == 0) return hipSuccess;
   hipLaunchKernelGGL(k_compose_combine, dim3(grid), dim3(TR_THREADS), 0, st, Tm, ch, tw, logn, out, row0,
                      row0 + nrows);
+  return hipGetLastError();
+}
+hipError_t launch_air_audit(hipStream_t st, const TraceDev& T, const AirAuditOut& O, const uint32_t* d_err) {
+  // the first-cell key holds the tape in 8 bits
+  if (T.n == 0 || T.tau < 0 || T.tau > 256 || !O.cnt || !O.viol || !O.rej) return hipErrorInvalidValue;
+  hipError_t e = hipMemsetAsync(O.cnt, 0, AUD_WORDS * 8, st);
+  if (e != hipSuccess) return e;
+  // AUD_ROWS_PER_LANE adjacent rows per lane, fewer when n is no multiple.
+  // SEZKP_AUDIT_ROWS=1|2|4 forces a form (read per launch: the parity test
+  // switches it).
+  const char* rw_s = getenv("SEZKP_AUDIT_ROWS");
+  int rw = rw_s ? atoi(rw_s) : AUD_ROWS_PER_LANE;
+  if (rw != 1 && rw != 2 && rw != 4) rw = AUD_ROWS_PER_LANE;
+  while (rw > 1 && T.n % rw) rw >>= 1;
+  const uint64_t wg_rows = (uint64_t)TR_THREADS * rw;
+  const unsigned g = (unsigned)std::min<uint64_t>((T.n + wg_rows - 1) / wg_rows, AUD_MAX_WGS);
+  if (rw == 4) hipLaunchKernelGGL(k_air_audit<4>, dim3(g), dim3(TR_THREADS), 0, st, T, O);
+  else if (rw == 2) hipLaunchKernelGGL(k_air_audit<2>, dim3(g), dim3(TR_THREADS), 0, st, T, O);
+  else hipLaunchKernelGGL(k_air_audit<1>, dim3(g), dim3(TR_THREADS), 0, st, T, O);
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  hipLaunchKernelGGL(k_air_audit_first, dim3(1), dim3(64), 0, st, T, O, d_err);
   return hipGetLastError();
 }
 hipError_t launch_col_open(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const uint32_t* outer_nodes,

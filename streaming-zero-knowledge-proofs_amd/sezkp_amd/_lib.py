@@ -36,7 +36,21 @@ EXPORTS = [
     "sezkp_fs_xof", "sezkp_ctx_upload_rows", "sezkp_shard_rows", "sezkp_blocks_decode_jsonl_meta",
     "sezkp_blocks_line_offsets", "sezkp_manifest_leaf_hashes", "sezkp_merkle_root_of_leaves",
     "sezkp_ctx_create_sharded_solo", "sezkp_blocks_decode_jsonl_lines", "sezkp_ctx_dict_plans",
+    "sezkp_ctx_air_audit", "sezkp_stark_v1_air_audit",
 ]
+
+AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
+
+
+class AirFamilyC(C.Structure):
+    _fields_ = [("cells", C.c_uint64), ("rows", C.c_uint64), ("first_row", C.c_uint64), ("first_tape", C.c_uint32),
+                ("pad", C.c_uint32), ("first_value", C.c_uint64)]
+
+
+class AirAuditC(C.Structure):
+    _fields_ = [("n_rows", C.c_uint64), ("tau", C.c_uint32), ("pad", C.c_uint32), ("rows_violating", C.c_uint64),
+                ("first_violating", C.c_uint64), ("rows_rejectable", C.c_uint64), ("first_rejectable", C.c_uint64),
+                ("fam", AirFamilyC * len(AIR_FAMILIES))]
 
 
 class CommStat(C.Structure):
@@ -174,6 +188,9 @@ def _load():
     L.sezkp_merkle_root_of_leaves.argtypes = [C.c_char_p, C.c_size_t, C.c_int32, C.c_char_p]
     L.sezkp_ctx_create_sharded_solo.restype = C.c_void_p
     L.sezkp_ctx_create_sharded_solo.argtypes = [C.c_int32, C.c_int32, C.c_int32] + E
+    L.sezkp_ctx_air_audit.argtypes = [C.c_void_p, C.POINTER(AirAuditC), C.c_void_p, C.c_void_p] + E
+    L.sezkp_stark_v1_air_audit.argtypes = [C.POINTER(BlockView), C.POINTER(AirAuditC), C.POINTER(Buf),
+                                           C.POINTER(Buf)] + E
     return L
 
 

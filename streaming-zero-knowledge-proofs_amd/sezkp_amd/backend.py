@@ -11,7 +11,7 @@ import json
 import struct
 from dataclasses import dataclass, field
 
-from ._lib import SEZKP_FLAG_STREAMING, Buf, SezkpError, check, lib, take_buf
+from ._lib import AIR_FAMILIES, SEZKP_FLAG_STREAMING, AirAuditC, Buf, SezkpError, check, lib, take_buf
 from .blocks import BlockSoA
 
 STAGES = ["expand", "col_commit", "col_outer", "compose", "intt", "lde_ntt", "deep", "layer0_tree",
@@ -46,6 +46,71 @@ class ProofArtifact:
             v = self.meta[k]
             out += text(k) + (text(v) if isinstance(v, str) else _head(0, int(v)))
         return bytes(out)
+
+
+NUM_QUERIES = 30  # params.rs:31
+NO_ROW = (1 << 64) - 1  # first_row / first_violating / first_rejectable when there is none
+
+
+@dataclass
+class AirAudit:
+    """Full-trace AIR audit (sezkp_ctx_air_audit): per constraint family
+    (mv_domain, head_range, slack_range, sym_range, boundary) a dict {cells,
+    rows, first_row, first_tape, first_value}, and two classes of rows:
+    violating (some cell of some family is non-zero) and rejectable (the
+    reference verifier fails when it queries the row). NO_ROW = no such row."""
+    n_rows: int
+    tau: int
+    families: dict
+    rows_violating: int
+    first_violating: int
+    rows_rejectable: int
+    first_rejectable: int
+    violating_bits: bytes | None = None
+    rejectable_bits: bytes | None = None
+
+    @property
+    def ok(self) -> bool:
+        return self.rows_violating == 0
+
+    def _rows(self, bits):
+        if bits is None:
+            return None
+        import numpy as np
+        b = np.unpackbits(np.frombuffer(bits, np.uint8), bitorder="little")[:self.n_rows]
+        return np.flatnonzero(b).astype(np.uint64)
+
+    def violating_rows(self):
+        """Ascending rows on which the AIR fails (None without bitmaps)."""
+        return self._rows(self.violating_bits)
+
+    def rejectable_rows(self):
+        """Ascending rows the verifier rejects when queried (None without bitmaps)."""
+        return self._rows(self.rejectable_bits)
+
+    def verify_reject_probability(self) -> float:
+        """Chance that verify fails: the NUM_QUERIES query rows are independent
+        draws mod n (params.rs:95-105)."""
+        return 1.0 - (1.0 - self.rows_rejectable / self.n_rows) ** NUM_QUERIES
+
+    def first_rejected_query(self, rows):
+        """The first of a proof's query rows that is rejectable (the row the
+        verifier's error names), or None. Needs the bitmaps."""
+        if self.rejectable_bits is None:
+            raise SezkpError(-1, "first_rejected_query needs an audit with bitmaps=True")
+        for r in rows:
+            r = int(r)
+            if 0 <= r < self.n_rows and (self.rejectable_bits[r >> 3] >> (r & 7)) & 1:
+                return r
+        return None
+
+    @staticmethod
+    def _from_c(a, vbits, rbits) -> "AirAudit":
+        fams = {name: {"cells": int(f.cells), "rows": int(f.rows), "first_row": int(f.first_row),
+                       "first_tape": int(f.first_tape), "first_value": int(f.first_value)}
+                for name, f in zip(AIR_FAMILIES, a.fam)}
+        return AirAudit(int(a.n_rows), int(a.tau), fams, int(a.rows_violating), int(a.first_violating),
+                        int(a.rows_rejectable), int(a.first_rejectable), vbits, rbits)
 
 
 def _head(major: int, v: int) -> bytes:
@@ -103,6 +168,18 @@ class StarkV1:
                                        bytes(manifest_root), err, 1024)
         check(rc, err)
 
+    @staticmethod
+    def air_audit(blocks: BlockSoA, bitmaps: bool = False) -> AirAudit:
+        """Full-trace AIR audit on device 0 (sezkp_stark_v1_air_audit); the
+        reference has no counterpart."""
+        blocks.check_shape()
+        a, vb, rb = AirAuditC(), Buf(), Buf()
+        err = C.create_string_buffer(1024)
+        rc = lib.sezkp_stark_v1_air_audit(C.byref(blocks.view()), C.byref(a), C.byref(vb) if bitmaps else None,
+                                          C.byref(rb) if bitmaps else None, err, 1024)
+        check(rc, err)
+        return AirAudit._from_c(a, take_buf(vb) if bitmaps else None, take_buf(rb) if bitmaps else None)
+
 
 class ProverContext:
     """Resident-input prover: upload once (trace image in HBM), prove many times."""
@@ -113,6 +190,7 @@ class ProverContext:
         if not self._h:
             raise SezkpError(-2, err.value.decode())
         self.tau = 0
+        self.n_rows = 0  # rows of the uploaded trace
         self.rank, self.world = 0, 1
 
     def upload(self, blocks: BlockSoA) -> None:
@@ -120,6 +198,7 @@ class ProverContext:
         err = C.create_string_buffer(1024)
         check(lib.sezkp_ctx_upload(self._h, C.byref(blocks.view()), err, 1024), err)
         self.tau = blocks.tau
+        self.n_rows = int(blocks.step_start[-1])
 
     def upload_rows(self, blocks: BlockSoA, row0: int, nrows: int) -> None:
         """Upload from a view whose step arrays hold only rows [row0, row0 +
@@ -132,6 +211,7 @@ class ProverContext:
         err = C.create_string_buffer(1024)
         check(lib.sezkp_ctx_upload_rows(self._h, C.byref(blocks.view()), row0, nrows, err, 1024), err)
         self.tau = blocks.tau
+        self.n_rows = int(blocks.step_start[-1])
 
     def stage(self, blocks: BlockSoA) -> None:
         """Pipelined upload of the next trace (same shape as the uploaded one):
@@ -150,6 +230,17 @@ class ProverContext:
                                   C.byref(pb), err, 1024), err)
         proof = take_buf(pb)
         return ProofArtifact("stark", bytes(manifest_root), proof, _meta(proof, self.tau, streaming))
+
+    def air_audit(self, bitmaps: bool = False) -> AirAudit:
+        """Audit the resident trace against the AIR on every row
+        (sezkp_ctx_air_audit); bitmaps=True also fetches the two row bitmaps."""
+        a = AirAuditC()
+        nbytes = (self.n_rows + 7) // 8
+        vb = C.create_string_buffer(nbytes) if bitmaps else None
+        rb = C.create_string_buffer(nbytes) if bitmaps else None
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_air_audit(self._h, C.byref(a), vb, rb, err, 1024), err)
+        return AirAudit._from_c(a, vb.raw if bitmaps else None, rb.raw if bitmaps else None)
 
     def prove_view(self, manifest_root: bytes) -> memoryview:
         """The proof bytes as a read-only view of the context's pinned host
@@ -260,6 +351,7 @@ class ShardedProverContext(ProverContext):
         import torch.distributed as dist
         err = C.create_string_buffer(1024)
         self.tau = 0
+        self.n_rows = 0
         self.rank, self.world = rank, world
         self._hc = None
         if comm == "rccl":
