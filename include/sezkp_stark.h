@@ -189,6 +189,22 @@ typedef struct sezkp_dict_plan_info {
   int64_t min;     /* smallest raw value of the column on this device's rows */
 } sezkp_dict_plan_info;
 int32_t sezkp_ctx_dict_plans(const sezkp_ctx* ctx, sezkp_dict_plan_info* out, int32_t max);
+/* Reuse of the dictionary tables across the proofs of one context. A column's
+ * tables depend on its value range (a head column's also on its tape's move
+ * range) and on the shape (rows, labels, table cap), not on the rows, so a
+ * prove rebuilds only the columns whose range differs from the one their
+ * tables were last built from; the decision is taken on the device, per
+ * column, and costs no copy or sync of its own. Anything else that the tables
+ * depend on (an upload of another shape, SEZKP_DICT_TAB_CAP, the plan-rows
+ * test hook) and any proof that failed make the next prove rebuild every
+ * column. SEZKP_DICT_CACHE=0 (read per prove) rebuilds every column on every
+ * prove; the proof bytes and the plans never depend on it.
+ * This reports the last completed prove: dictionary columns rebuilt and
+ * reused, and table entries rebuilt (all three 0 before the first prove of an
+ * upload, and always with SEZKP_NO_DICT=1). Returns SEZKP_OK, or
+ * SEZKP_E_INVALID for a null argument or while a proof is in flight. */
+int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* ctx, uint32_t* cols_rebuilt, uint32_t* cols_reused,
+                                   uint64_t* entries_rebuilt);
 
 /* ------------------------------------------------ full-trace AIR audit
  * Does the committed trace satisfy the AIR, on every row? The reference

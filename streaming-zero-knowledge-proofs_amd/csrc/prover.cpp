@@ -216,7 +216,39 @@ struct sezkp_ctx {
   DictPlan* d_dplans = nullptr;
   std::vector<sezkp_dict_plan_info> dict_info;  // col / kind / tape of each dictionary column (sezkp_ctx_dict_plans)
   bool have_plans = false;           // d_dplans holds the plans of a completed prove of this upload
+  // The dictionary tables and their reuse keys (DictCache) outlive an upload:
+  // they sit outside the workspace, sized for dict_cache_cols columns, so a
+  // later upload of the same shape finds the tables its columns' keys name.
   uint32_t* d_dtabs = nullptr;
+  DictKey* d_dkeys = nullptr;        // one block: the keys, the per-level words, the reuse flags
+  uint64_t* d_dlvl_seq = nullptr;
+  uint32_t* d_dreuse = nullptr;
+  uint32_t* d_dstatus = nullptr;     // behind the guard words (d_err + 16): 2 words per column
+  size_t dict_cache_cols = ~(size_t)0;
+  // dict_epoch: a new value whenever a host-side input of the tables changes
+  // (dict_hkey, dict_shape), after a proof that did not complete (dict_dirty)
+  // and for every proof with SEZKP_DICT_CACHE=0; dict_seq numbers the proofs
+  uint64_t dict_epoch = 1, dict_seq = 0;
+  // the host-side inputs of make_plan: n, and the rows this device commits
+  // (prove_body's row_lo / row_hi, from the rank's chunks), the hooks
+  struct DictHostKey {
+    uint64_t n = 0, nrows = 0, row0 = 0, plan_rows = 0;
+    uint32_t tab_cap = 0;
+    bool operator==(const DictHostKey& o) const {
+      return n == o.n && nrows == o.nrows && row0 == o.row0 && plan_rows == o.plan_rows && tab_cap == o.tab_cap;
+    }
+  } dict_hkey;
+  std::vector<uint8_t> dict_shape;   // the dictionary columns' templates and DictCols of the last upload
+  bool dict_dirty = false;
+  uint32_t dstat_rebuilt = 0, dstat_reused = 0;  // last completed prove (sezkp_ctx_dict_cache_stats)
+  uint64_t dstat_entries = 0;
+  void free_dict_cache() {
+    if (d_dtabs) (void)hipFree(d_dtabs);
+    if (d_dkeys) (void)hipFree(d_dkeys);
+    d_dtabs = nullptr;
+    d_dkeys = nullptr;
+    dict_cache_cols = ~(size_t)0;
+  }
   uint32_t* d_dlev = nullptr;        // dictionary columns' chunk levels 6..9 (openings)
   std::vector<uint32_t> dict_of;     // column -> dictionary index or NO_DICT
   uint32_t* d_outer = nullptr;
@@ -451,6 +483,7 @@ struct sezkp_ctx {
     free_all();
     release_spares();
     free_audit();
+    free_dict_cache();
     if (h_audit) (void)hipHostFree(h_audit);
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
@@ -760,8 +793,10 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   up(d_tmpl, tm.data(), tm.size());
   // column roots, then the guard words ([0] this rank's guard, [8 + r] rank
   // r's guard when sharded): one D2H copy
-  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16);
+  // and behind them the dictionary cache's status words (k_dict_plan)
+  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16 + 2 * dcols.size());
   d_err = d_colroots + (size_t)ncols * 8;
+  d_dstatus = d_err + 16;
   HIP_OR_THROW(hipMemset(d_err, 0, 64));
   d_tabs = dalloc<uint32_t>(tab_nodes * 8 + 8);
   n_tab_cols = (int)tab_cols.size();
@@ -783,7 +818,33 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   up(d_dcols, dcols.data(), dcols.size());
   d_dpart = dalloc<int64_t>(2 * dcols.size() * ((n + 4095) / 4096) + 2);
   d_dplans = dalloc<DictPlan>(dcols.size() + 1);
-  d_dtabs = dalloc<uint32_t>(dcols.size() * DICT_LEVELS * DICT_CAP * 8 + 8);
+  if (dcols.size() != dict_cache_cols) {
+    free_dict_cache();
+    dict_epoch++;
+    const size_t nd = dcols.size();
+    const size_t key_bytes = nd * sizeof(DictKey) + DICT_LEVELS * 8, cache_bytes = key_bytes + nd * 4 + 64;
+    HIP_OR_THROW(hipMalloc((void**)&d_dtabs, (nd * DICT_LEVELS * DICT_CAP * 8 + 8) * sizeof(uint32_t)));
+    // (if this one fails, d_dtabs stays allocated with dict_cache_cols unset:
+    // the next upload, or the destructor, frees it through free_dict_cache)
+    HIP_OR_THROW(hipMalloc((void**)&d_dkeys, cache_bytes));
+    HIP_OR_THROW(hipMemset(d_dkeys, 0, cache_bytes));  // epoch 0 and seq 0 are never passed
+    d_dlvl_seq = reinterpret_cast<uint64_t*>(d_dkeys + nd);
+    d_dreuse = reinterpret_cast<uint32_t*>(d_dlvl_seq + DICT_LEVELS);
+    dict_cache_cols = nd;
+  }
+  {  // what dict_entry reads of the columns besides the plan: label block and table slot
+    std::vector<uint8_t> shape(dcols.size() * (sizeof(ColTemplate) + sizeof(DictCol)));
+    uint8_t* p = shape.data();
+    for (const DictCol& d : dcols) {
+      memcpy(p, &tm[d.col], sizeof(ColTemplate));
+      memcpy(p + sizeof(ColTemplate), &d, sizeof(DictCol));
+      p += sizeof(ColTemplate) + sizeof(DictCol);
+    }
+    if (shape != dict_shape) {
+      dict_shape.swap(shape);
+      dict_epoch++;
+    }
+  }
   d_dlev = dalloc<uint32_t>(dcols.size() * (n >> COL_CHUNK_LOG2) * DLEV_NODES * 8 + 8);
   dict_of.assign(ncols, NO_DICT);
   for (size_t i = 0; i < dcols.size(); i++) dict_of[dcols[i].col] = (uint32_t)i;
@@ -989,7 +1050,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     h_proof = halloc<uint8_t>(hdr_bytes + PL.total);
     memcpy(h_proof, w.b.data(), hdr_bytes);
   }
-  h_small = halloc<uint32_t>((size_t)(ncols + k + 2) * 8);
+  h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + 2 * (size_t)n_dict);
   d_chal = dalloc<DevChal>(1);
   h_chal = halloc<DevChal>(1);
   d_dict_of = dalloc<uint32_t>((size_t)ncols);
@@ -1360,6 +1421,34 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     if (v > v_max) v = v_max;
     if (v >= COL_CHUNK_LOG2 && v <= 40) dict_plan_rows = 1ULL << v;
   }
+  // ---- dictionary table reuse (DictCache): the epoch moves with every
+  // host-side input of make_plan and dict_entry (the upload moves it for the
+  // templates, the DictCols and the table buffers), after a proof on this
+  // context that did not reach its end (its table launches may not all have
+  // run), and on every proof with SEZKP_DICT_CACHE=0 (read per prove), so that
+  // every column is rebuilt
+  {
+    const char* dce = getenv("SEZKP_DICT_CACHE");
+    const bool cache_off = dce && atoi(dce) == 0;
+    DictHostKey hk;
+    hk.n = n;
+    hk.nrows = row_hi - row_lo;
+    hk.row0 = row_lo;
+    hk.plan_rows = dict_plan_rows;
+    hk.tab_cap = dict_tab_cap;
+    if (cache_off || dict_dirty || !(hk == dict_hkey)) dict_epoch++;
+    dict_hkey = hk;
+    dict_dirty = true;  // until this proof completes
+    dict_seq++;
+  }
+  const DictCache dcache{d_dkeys, d_dreuse, d_dlvl_seq, d_dstatus, dict_epoch, dict_seq};
+  // (One launch of a workgroup per column instead of the five flat launches,
+  // chosen by the host when the last proof rebuilt nothing, was measured:
+  // 5.3 against 24.6 us for a warm proof, but 138 against 38 us with the head
+  // columns rebuilding and 317 against 104 us for a full rebuild, and a wrong
+  // guess at every change of trace: not kept, profiles/dict_cache/README.md.)
+  uint32_t st_rebuilt = 0;
+  uint64_t st_entries = 0;
   const int nguard = sharded ? comm->world : 1;
   auto check_guards = [&](const uint32_t* g_h, int ng) {
     for (int r = 0; r < ng; r++) {
@@ -1446,12 +1535,14 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // (the commit of the K <= 2 columns on a third stream beside table levels
     // 3..4 measured slower, round 6: profiles/r06/ab/dict_split_streams_ab.txt)
     ok(launch_dict_commit(st, T, d_tmpl, d_dcols, n_dict, d_dpart, d_dplans, d_dtabs, d_outer, outer_stride, row_lo,
-                          row_hi - row_lo, d_dlev, dict_tab_cap, dict_plan_rows),
+                          row_hi - row_lo, d_dlev, dcache, dict_tab_cap, dict_plan_rows),
        "col_commit_dict");
     HIP_OR_THROW(hipStreamWaitEvent(st, ev_cols, 0));
     // test hook: SEZKP_DEBUG_TRIP_GUARD=<rank> sets that rank's guard word, to
     // check that the failure is collective (tests/test_gpu_sharded.py)
-    static const char* trip = getenv("SEZKP_DEBUG_TRIP_GUARD");
+    // (read per prove: a good, a tripped and a good proof in one process,
+    // tests/test_gpu_dict_cache.py)
+    const char* trip = getenv("SEZKP_DEBUG_TRIP_GUARD");
     if (trip && atoi(trip) == rank) HIP_OR_THROW(hipMemsetAsync(d_err, 0x7f, 1, st));
     if (sharded) {
       // the chunk roots of every column and every rank's guard word in one
@@ -1474,13 +1565,20 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     ok(launch_tree_upper(st, &outer0, ncols, outer_stride, 8, 0), "col_outer");
     rec(3);
     // one copy: the column roots and the guard words stored right behind them
-    // (d_err = d_colroots + 8 ncols; sharded, every rank's word at d_err + 8)
-    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots, (size_t)ncols * 32 + 4 * (gofs + nguard), hipMemcpyDeviceToHost,
-                                st));
+    // (d_err = d_colroots + 8 ncols; sharded, every rank's word at d_err + 8),
+    // and the dictionary cache's status words behind the 16 guard words
+    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots,
+                                n_dict ? (size_t)ncols * 32 + 4 * (16 + 2 * (size_t)n_dict)
+                                       : (size_t)ncols * 32 + 4 * (gofs + nguard),
+                                hipMemcpyDeviceToHost, st));
   };
   auto host_1 = [&]() {
     const uint32_t* colroots_h = h_small;
     check_guards(h_small + 8 * ncols + gofs, nguard);
+    for (int c = 0; c < n_dict; c++) {
+      st_rebuilt += h_small[8 * ncols + 16 + 2 * c];
+      st_entries += h_small[8 * ncols + 16 + 2 * c + 1];
+    }
     std::vector<uint8_t> colroots((const uint8_t*)colroots_h, (const uint8_t*)colroots_h + (size_t)ncols * 32);
     for (int c = 0; c < ncols; c++) memcpy(h_proof + root_pos[c], colroots.data() + 32 * c, 32);
 
@@ -1941,6 +2039,10 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   host_ms[2] = t_last;
   host_ms[3] = std::chrono::duration<double, std::milli>(t_end - t_ser).count();
   have_plans = true;  // d_dplans: this proof's plans (sezkp_ctx_dict_plans)
+  dict_dirty = false;  // every table launch of this proof ran: its keys may validate
+  dstat_rebuilt = st_rebuilt;
+  dstat_reused = (uint32_t)n_dict - st_rebuilt;
+  dstat_entries = st_entries;
   return out;
 }
 
@@ -2261,6 +2363,17 @@ int32_t sezkp_ctx_dict_plans(const sezkp_ctx* cctx, sezkp_dict_plan_info* out, i
     o.min = pl[i].min;
   }
   return cnt;
+}
+int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* cctx, uint32_t* cols_rebuilt, uint32_t* cols_reused,
+                                   uint64_t* entries_rebuilt) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || !cols_rebuilt || !cols_reused || !entries_rebuilt) return SEZKP_E_INVALID;
+  if (ctx->busy()) return SEZKP_E_INVALID;  // the counts are rewritten by the proof in flight
+  const bool have = ctx->loaded && ctx->have_plans && ctx->n_dict != 0;
+  *cols_rebuilt = have ? ctx->dstat_rebuilt : 0;
+  *cols_reused = have ? ctx->dstat_reused : 0;
+  *entries_rebuilt = have ? ctx->dstat_entries : 0;
+  return SEZKP_OK;
 }
 int32_t sezkp_ctx_comm_stats(const sezkp_ctx* ctx, sezkp_comm_stat* out, int32_t max) {
   if (!ctx || !out || max <= 0) return 0;

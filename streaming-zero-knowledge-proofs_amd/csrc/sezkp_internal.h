@@ -247,6 +247,25 @@ struct DictPlan {
   uint32_t dR;
   uint32_t a;      // rows per commit lane = 2^(6 + a): dict_extra(K), lowered for few rows (k_dict_plan)
 };
+// Reuse of a context's dictionary tables across proofs (k_dict_plan). A
+// column's tables T_0..T_K depend on its range, on its tape's move range (head
+// columns) and on host-side inputs (n, the rows planned for, the table cap,
+// the column's label and table slot), never on the rows themselves. The key is
+// what the tables a context holds were last built from; `epoch` stands for
+// the host-side inputs: the host gives every change of them, and every proof
+// that did not complete, a new value, so a key of another epoch never matches.
+struct DictKey {
+  int64_t lo, hi, mlo, mhi;
+  uint64_t epoch;
+};
+struct DictCache {
+  DictKey* keys;      // per column
+  uint32_t* reuse;    // per column: 1 = the tables in place are this proof's
+  uint64_t* lvl_seq;  // per level: == seq when some column rebuilds the level in this proof
+  uint32_t* status;   // per column (rebuilt, entries rebuilt): goes home with the column roots
+  uint64_t epoch;
+  uint64_t seq;       // this proof's number on the context (never 0)
+};
 // Head delta plan: inside a block head[r] = head[r-1] + mv[r], so an aligned
 // 4-row head group is a function of (head[g], mv[g+1], mv[g+2], mv[g+3]):
 // TD[c0 + R (d1 + dR d2 + dR^2 d3)] = H(T_1[c0 + R c1], T_1[c2 + R c3]) with
@@ -314,22 +333,10 @@ hipError_t launch_col_commit(hipStream_t st, const TraceDev& T, const ColTemplat
 hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
                               int ndict, int64_t* d_part, DictPlan* d_plans, uint32_t* d_dtabs, uint32_t* outer_nodes,
                               uint64_t outer_stride_nodes, uint64_t row0, uint64_t nrows, uint32_t* d_dlev,
-                              uint32_t tab_cap = DICT_CAP, uint64_t plan_rows = 0);
-// the same in three steps, so the commit of the columns whose table level K
-// is built early can run beside the later levels: ranges + plans, table
-// levels [lvl_lo, lvl_hi), and the commit of the columns with kmin <= K <= kmax.
+                              const DictCache& dc, uint32_t tab_cap = DICT_CAP, uint64_t plan_rows = 0);
 // plan_rows != 0 (test hook SEZKP_TEST_DICT_PLAN_ROWS_LOG): the planner prices
 // the levels and sizes the lanes as on a device with plan_rows rows; the
 // ranges are still those of rows [row0, row0 + nrows)
-hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
-                               int ndict, int64_t* d_part, DictPlan* d_plans, uint64_t row0, uint64_t nrows,
-                               uint32_t tab_cap = DICT_CAP, uint64_t plan_rows = 0);
-hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
-                              const DictPlan* d_plans, uint32_t* d_dtabs, int lvl_lo, int lvl_hi);
-hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,
-                                   const DictCol* d_dcols, int ndict, const DictPlan* d_plans,
-                                   const uint32_t* d_dtabs, uint32_t* outer_nodes, uint64_t outer_stride_nodes,
-                                   uint64_t row0, uint64_t nrows, uint32_t* d_dlev, int kmin, int kmax);
 hipError_t launch_col_commit_pw(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const uint32_t* d_pw_cols,
                                 int n_pw_cols, const uint32_t* d_chunks, int nchunks, const uint32_t* tabs,
                                 uint32_t* outer_nodes, uint64_t outer_stride_nodes, uint32_t* d_err);

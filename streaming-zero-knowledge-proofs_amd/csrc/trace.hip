@@ -1628,15 +1628,38 @@ __global__ void __launch_bounds__(TR_THREADS) k_dict_range(TraceDev T, const Col
 // k_dict_range's last workgroup through agent-scope completion counters was
 // measured 100 us slower per proof in round 5: the release / acquire cache
 // maintenance of ~2000 workgroups disturbs the L2s the commit then gathers from.)
+// Then the reuse decision (DictCache): the column's tables T_0..T_K are a
+// function of (lo, hi, mlo, mhi) and of the host-side inputs that `epoch`
+// stands for, so a column whose stored key equals the new one keeps the tables
+// the context already holds; any other column stores the new key and is
+// rebuilt. A level some column rebuilds gets this proof's `seq` in its word.
 __global__ void __launch_bounds__(TR_THREADS) k_dict_plan(const int64_t* __restrict__ part, uint32_t nparts,
                                                           uint64_t n, uint64_t nrows, const DictCol* __restrict__ dcols,
-                                                          DictPlan* __restrict__ plans, uint32_t tab_cap) {
+                                                          DictPlan* __restrict__ plans, uint32_t tab_cap, DictCache dc) {
   __shared__ int64_t slo[TR_THREADS / 64], shi[TR_THREADS / 64];
   int64_t lo, hi, mlo = 0, mhi = -1;
   reduce_parts(part + 2 * (uint64_t)blockIdx.x * nparts, nparts, lo, hi, slo, shi);
   const uint32_t mvc = dcols[blockIdx.x].mv;
   if (mvc != NO_DICT) reduce_parts(part + 2 * (uint64_t)mvc * nparts, nparts, mlo, mhi, slo, shi);
-  if (threadIdx.x == 0) plans[blockIdx.x] = make_plan(lo, hi, mvc != NO_DICT, mlo, mhi, n, nrows, tab_cap);
+  if (threadIdx.x == 0) {
+    const DictPlan P = make_plan(lo, hi, mvc != NO_DICT, mlo, mhi, n, nrows, tab_cap);
+    plans[blockIdx.x] = P;
+    DictKey* key = dc.keys + blockIdx.x;
+    const DictKey old = *key;
+    const bool same = old.lo == lo && old.hi == hi && old.mlo == mlo && old.mhi == mhi && old.epoch == dc.epoch;
+    uint32_t entries = 0;
+    if (!same) {
+      *key = DictKey{lo, hi, mlo, mhi, dc.epoch};
+#pragma unroll
+      for (int k = 0; k < DICT_LEVELS; k++) {  // static indices only (pw is 0 above K)
+        entries += P.pw[k];
+        if (P.pw[k]) dc.lvl_seq[k] = dc.seq;  // every writer of one proof stores the same value
+      }
+    }
+    dc.reuse[blockIdx.x] = same ? 1u : 0u;
+    dc.status[2 * blockIdx.x] = same ? 0u : 1u;
+    dc.status[2 * blockIdx.x + 1] = entries;
+  }
 }
 
 // entry e of table level `lvl` of one dictionary column
@@ -1677,13 +1700,20 @@ __device__ __forceinline__ void dict_entry(const ColTemplate& ct, const DictCol&
 // Table level `lvl` of every dictionary column in one flat index space: each
 // WG sizes the level per column from the plans (prefix sums in LDS) and
 // grid-strides over all (column, entry) pairs, so a few hundred WGs share the
-// big levels evenly and the empty ones cost one plan scan.
+// big levels evenly and the empty ones cost one plan scan. A reused column
+// (k_dict_plan) counts 0 entries: its tables of the same key are in place. A
+// rebuilt column rebuilds every level 0..K it reads, and the levels above a
+// new, lower K (left from an earlier key) are never read. A level that no
+// column rebuilds in this proof costs a workgroup one load.
 constexpr int DICT_FLAT_MAX = 1024;  // columns one WG can index
 constexpr int DICT_FLAT_WGS = 2048;  // 8 waves per SIMD for the big levels
 __global__ void __launch_bounds__(TR_THREADS) k_dict_level(const ColTemplate* __restrict__ tmpl,
                                                            const DictCol* __restrict__ dcols,
                                                            const DictPlan* __restrict__ plans,
+                                                           const uint32_t* __restrict__ reuse,
+                                                           const uint64_t* __restrict__ lvl_seq, uint64_t seq,
                                                            uint32_t* __restrict__ tabs, int ndict, int lvl) {
+  if (lvl_seq[lvl] != seq) return;  // nothing to build at this level (uniform per grid)
   // columns [0, ndict) of the arrays passed (the host offsets them per chunk)
   __shared__ uint32_t off[DICT_FLAT_MAX + 1];
   const int tid = threadIdx.x;
@@ -1693,7 +1723,7 @@ __global__ void __launch_bounds__(TR_THREADS) k_dict_level(const ColTemplate* __
 #pragma unroll
     for (int k = 0; k < DICT_LEVELS; k++)  // static indices only (no scratch copy of P)
       if (k == lvl && lvl <= P.K) size = P.pw[k];
-    off[c + 1] = size;
+    off[c + 1] = reuse[c] ? 0 : size;
   }
   __syncthreads();
   if (tid == 0) {
@@ -1878,9 +1908,14 @@ static hipError_t dict_shape_ok(const TraceDev& T, uint64_t row0, uint64_t nrows
   if (row0 + nrows > T.n || (nrows != T.n && (row0 % DICT_WG_ROWS || nrows % DICT_WG_ROWS))) return hipErrorInvalidValue;
   return hipSuccess;
 }
-hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
-                               int ndict, int64_t* d_part, DictPlan* d_plans, uint64_t row0, uint64_t nrows,
-                               uint32_t tab_cap, uint64_t plan_rows) {
+// The dictionary commitment in three steps, in this order on one stream:
+// ranges + plans + reuse flags, table levels [lvl_lo, lvl_hi) of the columns
+// marked for rebuild, and the commit of the columns with kmin <= K <= kmax
+// (every level 0..K of a column must have been launched before its commit).
+static hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,
+                                      const DictCol* d_dcols, int ndict, int64_t* d_part, DictPlan* d_plans,
+                                      uint64_t row0, uint64_t nrows, uint32_t tab_cap, uint64_t plan_rows,
+                                      const DictCache& dc) {
   if (ndict == 0) return hipSuccess;
   hipError_t e = dict_shape_ok(T, row0, nrows);
   if (e != hipSuccess) return e;
@@ -1893,11 +1928,12 @@ hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTempl
                      row0, row0 + nrows, sweeps);
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_dict_plan, dim3(ndict), dim3(TR_THREADS), 0, st, d_part, nparts, T.n,
-                     plan_rows ? plan_rows : nrows, d_dcols, d_plans, tab_cap);
+                     plan_rows ? plan_rows : nrows, d_dcols, d_plans, tab_cap, dc);
   return hipGetLastError();
 }
-hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
-                              const DictPlan* d_plans, uint32_t* d_dtabs, int lvl_lo, int lvl_hi) {
+static hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
+                                     const DictPlan* d_plans, const DictCache& dc, uint32_t* d_dtabs, int lvl_lo,
+                                     int lvl_hi) {
   if (lvl_lo < 0 || lvl_hi > DICT_LEVELS) return hipErrorInvalidValue;
   for (int l = lvl_lo; l < lvl_hi; l++) {
     // one flat launch per level (and per DICT_FLAT_MAX columns): all WGs
@@ -1905,17 +1941,17 @@ hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const D
     for (int c0 = 0; c0 < ndict; c0 += DICT_FLAT_MAX) {
       const int nc = ndict - c0 < DICT_FLAT_MAX ? ndict - c0 : DICT_FLAT_MAX;
       hipLaunchKernelGGL(k_dict_level, dim3(DICT_FLAT_WGS), dim3(TR_THREADS), 0, st, d_tmpl, d_dcols + c0,
-                         d_plans + c0, d_dtabs, nc, l);
+                         d_plans + c0, dc.reuse + c0, dc.lvl_seq, dc.seq, d_dtabs, nc, l);
       hipError_t e = hipGetLastError();
       if (e != hipSuccess) return e;
     }
   }
   return hipSuccess;
 }
-hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,
-                                   const DictCol* d_dcols, int ndict, const DictPlan* d_plans,
-                                   const uint32_t* d_dtabs, uint32_t* outer_nodes, uint64_t outer_stride_nodes,
-                                   uint64_t row0, uint64_t nrows, uint32_t* d_dlev, int kmin, int kmax) {
+static hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,
+                                          const DictCol* d_dcols, int ndict, const DictPlan* d_plans,
+                                          const uint32_t* d_dtabs, uint32_t* outer_nodes, uint64_t outer_stride_nodes,
+                                          uint64_t row0, uint64_t nrows, uint32_t* d_dlev, int kmin, int kmax) {
   if (ndict == 0) return hipSuccess;
   hipError_t e = dict_shape_ok(T, row0, nrows);
   if (e != hipSuccess) return e;
@@ -1928,9 +1964,11 @@ hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColT
 hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
                               int ndict, int64_t* d_part, DictPlan* d_plans, uint32_t* d_dtabs, uint32_t* outer_nodes,
                               uint64_t outer_stride_nodes, uint64_t row0, uint64_t nrows, uint32_t* d_dlev,
-                              uint32_t tab_cap, uint64_t plan_rows) {
-  hipError_t e = launch_dict_prepare(st, T, d_tmpl, d_dcols, ndict, d_part, d_plans, row0, nrows, tab_cap, plan_rows);
-  if (e == hipSuccess && ndict) e = launch_dict_levels(st, d_tmpl, d_dcols, ndict, d_plans, d_dtabs, 0, DICT_LEVELS);
+                              const DictCache& dc, uint32_t tab_cap, uint64_t plan_rows) {
+  hipError_t e =
+      launch_dict_prepare(st, T, d_tmpl, d_dcols, ndict, d_part, d_plans, row0, nrows, tab_cap, plan_rows, dc);
+  if (e == hipSuccess && ndict)
+    e = launch_dict_levels(st, d_tmpl, d_dcols, ndict, d_plans, dc, d_dtabs, 0, DICT_LEVELS);
   if (e == hipSuccess)
     e = launch_dict_commit_cols(st, T, d_tmpl, d_dcols, ndict, d_plans, d_dtabs, outer_nodes, outer_stride_nodes, row0,
                                 nrows, d_dlev, -1, DICT_LEVELS);

@@ -296,6 +296,16 @@ class ProverContext:
             raise SezkpError(n, f"dict_plans: {why}")
         return [{f: int(getattr(buf[i], f)) for f, _ in DictPlanInfo._fields_} for i in range(n)]
 
+    def dict_cache_stats(self) -> dict:
+        """The dictionary table reuse of the last completed prove:
+        {cols_rebuilt, cols_reused, entries_rebuilt} (sezkp_ctx_dict_cache_stats;
+        all 0 before the first prove of an upload and with SEZKP_NO_DICT=1)."""
+        rebuilt, reused, entries = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        rc = lib.sezkp_ctx_dict_cache_stats(self._h, C.byref(rebuilt), C.byref(reused), C.byref(entries))
+        if rc < 0:
+            raise SezkpError(rc, "dict_cache_stats: a proof is in flight on this context (or the context is closed)")
+        return {"cols_rebuilt": rebuilt.value, "cols_reused": reused.value, "entries_rebuilt": entries.value}
+
     def dist_ntt(self, local, scratch=None, inverse: bool = False, sync: bool = True):
         """Distributed four-step NTT of n = world * local.numel() points, in
         place on `local` (a device u64/i64 tensor; layouts in sezkp_stark.h,
