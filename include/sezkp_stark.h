@@ -275,6 +275,64 @@ int32_t sezkp_ctx_air_audit(sezkp_ctx* ctx, sezkp_air_audit* out, uint8_t* viola
 int32_t sezkp_stark_v1_air_audit(const sezkp_block_view* blocks, sezkp_air_audit* out, sezkp_buf* violating_bits,
                                  sezkp_buf* rejectable_bits, char* err, size_t err_len);
 
+/* ------------------------------------------------ batch verification on the GPU
+ * sezkp_stark_v1_verify spends nearly all of its time in BLAKE3: a T = 2^21,
+ * tau = 8 proof asks for about 5,940 independent Merkle chains (two per column
+ * opening, two per FRI pair and layer) of about 69,000 compressions. Here the
+ * host parses each proof once (offsets only) and lists every chain as a job;
+ * one kernel (k_verify_chains, one chain per lane) hashes the chains of the
+ * whole batch and writes a word per job; the host then walks the checks of
+ * sezkp_stark_v1_verify in their order (the transcript, the AIR sums of the
+ * opened rows and the fold relation stay on the host) and reads that word
+ * wherever the host verifier would hash a path. For every proof out[i].code and
+ * out[i].msg are what sezkp_stark_v1_verify returns and writes for the same
+ * bytes, root and tau (msg is empty on SEZKP_OK), decode errors and an empty
+ * proof included.
+ *   manifest_root  32 bytes or NULL: the "manifest root mismatch" check
+ *   tau            0: not checked; else "tau mismatch vs. block windows"
+ * The return value reports on the call: SEZKP_OK when every proof received a
+ * verdict (n = 0 included); SEZKP_E_INVALID for a null ctx, null proofs or out
+ * with n > 0, a proof with null bytes and len > 0, a proof in flight on the
+ * context, or a sharded context; SEZKP_E_DEVICE for a HIP failure.
+ * Works with or without an uploaded trace and touches neither the trace image
+ * nor the prover's workspace: its pinned staging and device buffers are the
+ * context's own, grow on demand and are kept. Runs on the context's stream and
+ * synchronises it. A batch whose proofs exceed an internal cap (256 MiB) is
+ * processed in slices inside the call; SEZKP_VERIFY_CHUNK_BYTES (read per
+ * call) lowers the cap; a proof larger than the cap is a slice of its own.
+ * Chains of more than 1024 siblings (no honest proof has more than 64) are
+ * hashed by the host inside the same call. Extends the reference, whose
+ * verifier is single-threaded CPU code. */
+typedef struct sezkp_proof_ref {
+  const uint8_t* bytes;
+  size_t len;
+  const uint8_t* manifest_root;
+  uint32_t tau;
+  uint32_t pad;
+} sezkp_proof_ref;
+typedef struct sezkp_verify_result {
+  int32_t code;
+  uint32_t pad;
+  char msg[248];
+} sezkp_verify_result;
+int32_t sezkp_ctx_verify_batch(sezkp_ctx* ctx, const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out,
+                               char* err, size_t err_len);
+/* Stateless: device 0. Null arguments and n = 0 are answered before any
+ * device is touched. */
+int32_t sezkp_stark_v1_verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out, char* err,
+                                    size_t err_len);
+/* Where the last sezkp_ctx_verify_batch on the context spent its time (ms,
+ * summed over its slices; always measured): host parse and job building,
+ * packing the pinned staging block, the host's wait for the device part, the
+ * H2D copy, the kernel and the result readback (HIP events on the stream), the
+ * checks, the whole call, then the number of jobs and of slices. Returns the
+ * number of values written. */
+enum {
+  SEZKP_VT_PARSE, SEZKP_VT_PACK, SEZKP_VT_DEVICE_WALL, SEZKP_VT_H2D, SEZKP_VT_KERNEL, SEZKP_VT_D2H, SEZKP_VT_DECIDE,
+  SEZKP_VT_WALL, SEZKP_VT_JOBS, SEZKP_VT_SLICES, SEZKP_VERIFY_TIMES
+};
+int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max);
+
 /* ------------------------------------------------ sharded proving (one proof, P GPUs)
  * One process per GPU; every rank uploads the same blocks and calls prove()
  * with the same manifest root; every rank returns the identical proof bytes.

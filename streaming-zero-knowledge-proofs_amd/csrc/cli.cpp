@@ -1,6 +1,7 @@
 // cli.cpp — `sezkp-cli` drop-in for the STARK path on MI355X:
 //   prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]
-//   verify --backend stark --blocks B --manifest M --proof P [--assume-committed]
+//   verify --backend stark --blocks B --manifest M --proof P [--assume-committed] [--gpu]
+//          (--gpu: the Merkle paths are hashed on device 0, sezkp_stark_v1_verify_batch; same output)
 //   commit --blocks B(.cbor|.json|.jsonl|.ndjson) --out M
 //   verify-commit --blocks B --manifest M
 //   export-jsonl --input B(.cbor|.json|.jsonl|.ndjson) --output B.jsonl
@@ -101,7 +102,7 @@ std::string pretty_artifact(const Artifact& a) {
 
 struct Args {
   std::string cmd, backend = "stark", blocks, manifest, out, proof, input;
-  bool stream = false, assume = false, json = false;
+  bool stream = false, assume = false, json = false, gpu = false;
   std::string t = "32", b = "4", tau = "2";  // simulate defaults (main.rs:87-100)
 };
 
@@ -223,7 +224,18 @@ int cmd_verify(const Args& a) {
     return 1;
   }
   char msg[512] = {0};
-  if (sezkp_stark_v1_verify(art.proof_bytes.data(), art.proof_bytes.size(), &bs.view, mroot, msg, sizeof msg)) {
+  if (a.gpu && !(bs.view.n_blocks && bs.view.tau == 0)) {  // a tau of 0 to check: only the host call can say it
+    sezkp_proof_ref ref{art.proof_bytes.data(), art.proof_bytes.size(), mroot, bs.view.n_blocks ? bs.view.tau : 0, 0};
+    sezkp_verify_result res{};
+    if (sezkp_stark_v1_verify_batch(&ref, 1, &res, msg, sizeof msg)) {
+      fprintf(stderr, "Error: stark-v1 verification on the GPU could not run: %s\n", msg);
+      return 1;
+    }
+    if (res.code) {
+      fprintf(stderr, "Error: stark-v1 verification failed: %s\n", res.msg);
+      return 1;
+    }
+  } else if (sezkp_stark_v1_verify(art.proof_bytes.data(), art.proof_bytes.size(), &bs.view, mroot, msg, sizeof msg)) {
     fprintf(stderr, "Error: stark-v1 verification failed: %s\n", msg);
     return 1;
   }
@@ -401,7 +413,7 @@ int cmd_audit(const Args& a) {
 void usage() {
   fprintf(stderr,
           "usage: sezkp-cli prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]\n"
-          "       sezkp-cli verify --backend stark --blocks B --manifest M --proof P [--assume-committed]\n"
+          "       sezkp-cli verify --backend stark --blocks B --manifest M --proof P [--assume-committed] [--gpu]\n"
           "       sezkp-cli commit --blocks B --out M\n"
           "       sezkp-cli verify-commit --blocks B --manifest M\n"
           "       sezkp-cli export-jsonl --input B --output B.jsonl\n"
@@ -434,6 +446,7 @@ int main(int argc, char** argv) {
     else if (s == "--stream") a.stream = true;
     else if (s == "--assume-committed") a.assume = true;
     else if (s == "--json") a.json = true;
+    else if (s == "--gpu") a.gpu = true;
     else { fprintf(stderr, "unknown argument %s\n", s.c_str()); usage(); return 2; }
   }
   for (auto& c : a.backend) c = (char)tolower((unsigned char)c);

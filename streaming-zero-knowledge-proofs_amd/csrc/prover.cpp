@@ -27,6 +27,7 @@
 #include "comm.h"
 #include "host_crypto.h"
 #include "sezkp_internal.h"
+#include "verify_plan.h"
 
 using namespace sezkp;
 
@@ -358,6 +359,28 @@ struct sezkp_ctx {
     audit_n = 0;
   }
 
+  // Batch verification (sezkp_ctx_verify_batch): one pinned block and its
+  // device twin hold a slice's proof bytes, an aligned copy of the column
+  // roots, the job table and the result words, in that order; the label
+  // templates (the same for every proof) stay on the device. Like the audit's
+  // buffers they live outside the upload workspace: they grow on demand and
+  // are kept, and neither upload nor prove sees them.
+  uint8_t* d_vfy = nullptr;
+  uint8_t* h_vfy = nullptr;
+  size_t vfy_cap = 0;
+  VerifyLabel* d_vlabels = nullptr;
+  uint64_t n_vlabels = 0;
+  hipEvent_t vev[4]{};
+  double vfy_ms[SEZKP_VERIFY_TIMES]{};
+  void free_verify() {
+    if (d_vfy) (void)hipFree(d_vfy);
+    if (h_vfy) (void)hipHostFree(h_vfy);
+    if (d_vlabels) (void)hipFree(d_vlabels);
+    for (auto& e : vev)
+      if (e) (void)hipEventDestroy(e);
+  }
+  void verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out);
+
   static void* take_spare(std::multimap<size_t, void*>& m, size_t bytes) {
     auto it = m.find(bytes);
     if (it == m.end()) return nullptr;
@@ -483,6 +506,7 @@ struct sezkp_ctx {
     free_all();
     release_spares();
     free_audit();
+    free_verify();
     free_dict_cache();
     if (h_audit) (void)hipHostFree(h_audit);
     for (auto& e : ev)
@@ -1272,6 +1296,152 @@ void sezkp_ctx::air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t
     a.first_tape = key == ~0ull ? 0 : (uint32_t)(key & 0xFF);
     a.first_value = c[AUD_VALUE + f];
   }
+}
+
+// Batch verification (sezkp_stark.h): the parse and the checks are verify.cpp's
+// (verify_plan.h); here the jobs of a slice of proofs go to k_verify_chains
+// and the checks then read its result words. Proofs whose verdict the parse
+// already gave (a decode error, a manifest root mismatch) send nothing.
+void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out) {
+  if (sharded()) throw Err{SEZKP_E_INVALID, "verify_batch: not on a sharded context (use a single-device context)"};
+  using clk = std::chrono::steady_clock;
+  auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
+  const auto t_call = clk::now();
+  for (auto& v : vfy_ms) v = 0;
+  HIP_OR_THROW(hipSetDevice(device));
+  size_t cap = (size_t)256 << 20;  // proof bytes per slice
+  if (const char* e = getenv("SEZKP_VERIFY_CHUNK_BYTES")) {
+    const unsigned long long v = strtoull(e, nullptr, 10);
+    if (v > 0 && v < cap) cap = (size_t)v;
+  }
+  constexpr uint64_t MAX_SLICE_JOBS = 1ull << 28;
+  for (auto& e : vev)
+    if (!e) HIP_OR_THROW(hipEventCreate(&e));
+  std::vector<VerifyItem> items;
+  std::vector<size_t> place;  // a proof's first byte in the slice's bytes
+  uint32_t i = 0;
+  while (i < n) {
+    auto t0 = clk::now();
+    items.clear();
+    place.clear();
+    size_t nbytes = 0, nroots = 0;
+    uint64_t njobs = 0, ndev = 0, nlabels = 0;
+    uint32_t j = i;
+    for (; j < n; j++) {
+      // a proof that does not fit the rest of the slice starts the next one; the first always fits
+      if (j > i && (nbytes + proofs[j].len + 8 > cap || njobs > MAX_SLICE_JOBS)) break;
+      items.emplace_back();
+      VerifyItem& it = items.back();
+      it.ref = proofs[j];
+      it.check_tau = proofs[j].tau != 0;
+      it.tau_want = proofs[j].tau;
+      static const uint8_t none = 0;
+      if (!it.ref.bytes) it.ref.bytes = &none;  // len == 0 (checked by the caller): an empty proof
+      verify_parse(it);
+      size_t at = 0;
+      if (!it.jobs.empty()) {
+        // body 8-byte aligned: every value and sibling then is (all fields after the header are 8 or 32 bytes)
+        at = nbytes + (8 - (nbytes + it.hdr_len) % 8) % 8;
+        nbytes = at + it.ref.len;
+        nroots += it.col_roots.size();
+        njobs += it.jobs.size();
+        nlabels = std::max(nlabels, it.n_dev_labels);
+        for (const VerifyJob& job : it.jobs) ndev += !(job.tag & VJ_HOST);
+      }
+      place.push_back(at);
+    }
+    if (njobs > 0xFFFFFFFFull) throw Err{SEZKP_E_INVALID, "verify_batch: a proof with more than 2^32 Merkle paths"};
+    vfy_ms[SEZKP_VT_PARSE] += ms_since(t0);
+    const uint32_t* result = nullptr;
+    if (ndev) {
+      t0 = clk::now();
+      const size_t roots_off = (nbytes + 63) & ~(size_t)63;
+      const size_t jobs_off = roots_off + 32 * nroots;
+      const size_t res_off = jobs_off + sizeof(VerifyJobDev) * (size_t)ndev;
+      const size_t total = res_off + 4 * (size_t)njobs;
+      if (total > vfy_cap) {
+        HIP_OR_THROW(hipStreamSynchronize(st));
+        if (d_vfy) (void)hipFree(d_vfy);
+        if (h_vfy) (void)hipHostFree(h_vfy);
+        d_vfy = h_vfy = nullptr;
+        vfy_cap = 0;
+        const size_t want = total + total / 4;
+        HIP_OR_THROW(hipMalloc(&d_vfy, want));
+        HIP_OR_THROW(hipHostMalloc(&h_vfy, want, hipHostMallocDefault));
+        vfy_cap = want;
+      }
+      if (nlabels > n_vlabels) {
+        std::vector<VerifyLabel> tl((size_t)nlabels);
+        for (uint64_t l = 0; l < nlabels; l++) verify_label_template(l, tl[(size_t)l]);
+        HIP_OR_THROW(hipStreamSynchronize(st));
+        if (d_vlabels) (void)hipFree(d_vlabels);
+        d_vlabels = nullptr;
+        n_vlabels = 0;
+        HIP_OR_THROW(hipMalloc(&d_vlabels, sizeof(VerifyLabel) * tl.size()));
+        HIP_OR_THROW(hipMemcpy(d_vlabels, tl.data(), sizeof(VerifyLabel) * tl.size(), hipMemcpyHostToDevice));
+        n_vlabels = nlabels;
+      }
+      VerifyJobDev* hj = reinterpret_cast<VerifyJobDev*>(h_vfy + jobs_off);
+      size_t r0 = 0, j0 = 0, d0 = 0;
+      for (size_t k = 0; k < items.size(); k++) {
+        const VerifyItem& it = items[k];
+        if (it.jobs.empty()) continue;
+        memcpy(h_vfy + place[k], it.ref.bytes, it.ref.len);
+        for (size_t c = 0; c < it.col_roots.size(); c++)
+          memcpy(h_vfy + roots_off + 32 * (r0 + c), it.ref.bytes + it.col_roots[c], 32);
+        for (const VerifyJob& src : it.jobs) {
+          const uint32_t out_word = (uint32_t)j0++;
+          if (src.tag & VJ_HOST) continue;
+          VerifyJobDev& d = hj[d0++];  // proof order: ordering by sibling count was measured and not kept
+          d.leaf = src.leaf + place[k];
+          d.sibs = src.sibs + place[k];
+          d.root = (src.tag & VJ_ROOT_TABLE) ? 32 * (r0 + src.root) : src.root + place[k];
+          d.index = src.index;
+          d.nsib = (uint32_t)src.nsib;
+          d.out = out_word;
+          d.tag = src.tag;
+        }
+        r0 += it.col_roots.size();
+      }
+      vfy_ms[SEZKP_VT_PACK] += ms_since(t0);
+      t0 = clk::now();
+      HIP_OR_THROW(hipEventRecord(vev[0], st));
+      HIP_OR_THROW(hipMemcpyAsync(d_vfy, h_vfy, res_off, hipMemcpyHostToDevice, st));
+      HIP_OR_THROW(hipEventRecord(vev[1], st));
+      HIP_OR_THROW(launch_verify_chains(st, d_vfy, reinterpret_cast<const VerifyJobDev*>(d_vfy + jobs_off),
+                                        d_vfy + roots_off, d_vlabels, (uint32_t)ndev,
+                                        reinterpret_cast<uint32_t*>(d_vfy + res_off)));
+      HIP_OR_THROW(hipEventRecord(vev[2], st));
+      HIP_OR_THROW(hipMemcpyAsync(h_vfy + res_off, d_vfy + res_off, 4 * (size_t)njobs, hipMemcpyDeviceToHost, st));
+      HIP_OR_THROW(hipEventRecord(vev[3], st));
+      HIP_OR_THROW(hipStreamSynchronize(st));
+      vfy_ms[SEZKP_VT_DEVICE_WALL] += ms_since(t0);
+      float f = 0;
+      HIP_OR_THROW(hipEventElapsedTime(&f, vev[0], vev[1]));
+      vfy_ms[SEZKP_VT_H2D] += f;
+      HIP_OR_THROW(hipEventElapsedTime(&f, vev[1], vev[2]));
+      vfy_ms[SEZKP_VT_KERNEL] += f;
+      HIP_OR_THROW(hipEventElapsedTime(&f, vev[2], vev[3]));
+      vfy_ms[SEZKP_VT_D2H] += f;
+      result = reinterpret_cast<const uint32_t*>(h_vfy + res_off);
+    }
+    t0 = clk::now();
+    size_t j0 = 0;
+    for (size_t k = 0; k < items.size(); k++) {
+      VerifyItem& it = items[k];
+      verify_decide(it, result ? result + j0 : nullptr);
+      j0 += it.jobs.size();
+      sezkp_verify_result& o = out[i + k];
+      o.code = it.code;
+      o.pad = 0;
+      snprintf(o.msg, sizeof o.msg, "%s", it.code == SEZKP_OK ? "" : it.msg.c_str());
+    }
+    vfy_ms[SEZKP_VT_DECIDE] += ms_since(t0);
+    vfy_ms[SEZKP_VT_JOBS] += (double)njobs;
+    vfy_ms[SEZKP_VT_SLICES] += 1;
+    i = j;
+  }
+  vfy_ms[SEZKP_VT_WALL] = ms_since(t_call);
 }
 
 size_t sezkp_ctx::prove(const uint8_t mroot[32]) {
@@ -2254,6 +2424,44 @@ int32_t sezkp_ctx_air_audit(sezkp_ctx* ctx, sezkp_air_audit* out, uint8_t* viola
   }
 }
 
+static bool verify_batch_args_ok(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out, char* err,
+                                 size_t err_len) {
+  if (n && (!proofs || !out)) {
+    set_err(err, err_len, "null argument");
+    return false;
+  }
+  for (uint32_t i = 0; i < n; i++)
+    if (!proofs[i].bytes && proofs[i].len) {
+      set_err(err, err_len, "proof " + std::to_string(i) + ": null bytes with a non-zero length");
+      return false;
+    }
+  return true;
+}
+
+int32_t sezkp_ctx_verify_batch(sezkp_ctx* ctx, const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out,
+                               char* err, size_t err_len) {
+  try {
+    if (!ctx) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (!verify_batch_args_ok(proofs, n, out, err, err_len)) return SEZKP_E_INVALID;
+    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    ctx->verify_batch(proofs, n, out);
+    return SEZKP_OK;
+  } catch (const Err& e) {
+    set_err(err, err_len, e.msg);
+    return e.code;
+  } catch (const std::exception& e) {
+    set_err(err, err_len, e.what());
+    return SEZKP_E_NOMEM;
+  }
+}
+
+int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max) {
+  if (!ctx || !out_ms) return 0;
+  int32_t k = 0;
+  for (; k < SEZKP_VERIFY_TIMES && k < max; k++) out_ms[k] = ctx->vfy_ms[k];
+  return k;
+}
+
 int32_t sezkp_ctx_prove_borrow(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, const uint8_t** data,
                                size_t* len, char* err, size_t err_len) {
   (void)flags;
@@ -2497,6 +2705,17 @@ int32_t sezkp_stark_v1_air_audit(const sezkp_block_view* blocks, sezkp_air_audit
       }
     }
   }
+  sezkp_ctx_destroy(ctx);
+  return rc;
+}
+
+int32_t sezkp_stark_v1_verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out, char* err,
+                                    size_t err_len) {
+  if (!verify_batch_args_ok(proofs, n, out, err, err_len)) return SEZKP_E_INVALID;  // before any device is touched
+  if (n == 0) return SEZKP_OK;
+  sezkp_ctx* ctx = sezkp_ctx_create(0, err, err_len);
+  if (!ctx) return SEZKP_E_DEVICE;
+  const int32_t rc = sezkp_ctx_verify_batch(ctx, proofs, n, out, err, err_len);
   sezkp_ctx_destroy(ctx);
   return rc;
 }

@@ -366,6 +366,13 @@ struct MerkleLevels {
 // q paths of `depth` siblings: path i, level l = sibling of (idx[i] % len[0]) >> l
 hipError_t launch_merkle_paths(hipStream_t st, const uint32_t* nodes, const MerkleLevels& L, const uint64_t* idx,
                                uint32_t q, uint32_t* out);
+// Merkle chains of a batch of proofs (verify_gpu.hip, verify_plan.h): job i's
+// chain over `bytes` ends in its root (in `bytes`, or in `roots` with
+// VJ_ROOT_TABLE) -> result[jobs[i].out] = 1, else 0
+struct VerifyJobDev;
+struct VerifyLabel;
+hipError_t launch_verify_chains(hipStream_t st, const uint8_t* bytes, const VerifyJobDev* jobs, const uint8_t* roots,
+                                const VerifyLabel* labels, uint32_t njobs, uint32_t* result);
 // Sharded LDE layout change (see prover.cpp, prove_sharded): cyclic coset
 // values of rank g (index g + P*j) <-> runs of S = 2^12 consecutive indices.
 hipError_t launch_cyc_pack(hipStream_t st, const uint64_t* cyc, uint64_t* send, uint64_t M, int logP);

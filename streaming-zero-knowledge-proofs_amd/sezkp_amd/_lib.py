@@ -37,6 +37,7 @@ EXPORTS = [
     "sezkp_blocks_line_offsets", "sezkp_manifest_leaf_hashes", "sezkp_merkle_root_of_leaves",
     "sezkp_ctx_create_sharded_solo", "sezkp_blocks_decode_jsonl_lines", "sezkp_ctx_dict_plans",
     "sezkp_ctx_air_audit", "sezkp_stark_v1_air_audit", "sezkp_ctx_dict_cache_stats",
+    "sezkp_ctx_verify_batch", "sezkp_stark_v1_verify_batch", "sezkp_ctx_verify_times",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -51,6 +52,20 @@ class AirAuditC(C.Structure):
     _fields_ = [("n_rows", C.c_uint64), ("tau", C.c_uint32), ("pad", C.c_uint32), ("rows_violating", C.c_uint64),
                 ("first_violating", C.c_uint64), ("rows_rejectable", C.c_uint64), ("first_rejectable", C.c_uint64),
                 ("fam", AirFamilyC * len(AIR_FAMILIES))]
+
+
+class ProofRef(C.Structure):  # sezkp_proof_ref
+    _fields_ = [("bytes", C.c_void_p), ("len", C.c_size_t), ("manifest_root", C.c_void_p), ("tau", C.c_uint32),
+                ("pad", C.c_uint32)]
+
+
+class VerifyResultC(C.Structure):  # sezkp_verify_result
+    _fields_ = [("code", C.c_int32), ("pad", C.c_uint32), ("msg", C.c_char * 248)]
+
+
+# sezkp_ctx_verify_times, in the order of the SEZKP_VT_* values
+VERIFY_TIMES = ("parse_ms", "pack_ms", "device_wall_ms", "h2d_ms", "kernel_ms", "d2h_ms", "decide_ms", "wall_ms",
+                "jobs", "slices")
 
 
 class CommStat(C.Structure):
@@ -193,6 +208,9 @@ def _load():
     L.sezkp_ctx_air_audit.argtypes = [C.c_void_p, C.POINTER(AirAuditC), C.c_void_p, C.c_void_p] + E
     L.sezkp_stark_v1_air_audit.argtypes = [C.POINTER(BlockView), C.POINTER(AirAuditC), C.POINTER(Buf),
                                            C.POINTER(Buf)] + E
+    L.sezkp_ctx_verify_batch.argtypes = [C.c_void_p, C.POINTER(ProofRef), C.c_uint32, C.POINTER(VerifyResultC)] + E
+    L.sezkp_stark_v1_verify_batch.argtypes = [C.POINTER(ProofRef), C.c_uint32, C.POINTER(VerifyResultC)] + E
+    L.sezkp_ctx_verify_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
     return L
 
 

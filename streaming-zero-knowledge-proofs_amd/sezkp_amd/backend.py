@@ -11,7 +11,8 @@ import json
 import struct
 from dataclasses import dataclass, field
 
-from ._lib import AIR_FAMILIES, SEZKP_FLAG_STREAMING, AirAuditC, Buf, SezkpError, check, lib, take_buf
+from ._lib import (AIR_FAMILIES, SEZKP_FLAG_STREAMING, VERIFY_TIMES, AirAuditC, Buf, ProofRef, SezkpError,
+                   VerifyResultC, check, lib, take_buf)
 from .blocks import BlockSoA
 
 STAGES = ["expand", "col_commit", "col_outer", "compose", "intt", "lde_ntt", "deep", "layer0_tree",
@@ -113,6 +114,40 @@ class AirAudit:
                         int(a.rows_rejectable), int(a.first_rejectable), vbits, rbits)
 
 
+@dataclass
+class VerifyResult:
+    """One proof's verdict from verify_batch: the code and message
+    sezkp_stark_v1_verify gives for the same bytes, root and tau."""
+    ok: bool
+    code: int
+    message: str
+
+
+def _verify_batch(call, proofs, manifest_roots, taus) -> list:
+    """call(refs, n, out, err, 1024) -> rc over sezkp_proof_ref[n]."""
+    proofs = list(proofs)
+    n = len(proofs)
+    roots = list(manifest_roots) if manifest_roots is not None else [None] * n
+    taus = list(taus) if taus is not None else [0] * n
+    if len(roots) != n or len(taus) != n:
+        raise SezkpError(-1, "verify_batch: manifest_roots and taus must have one entry per proof")
+    refs, out, keep = (ProofRef * n)(), (VerifyResultC * n)(), []
+    for i, p in enumerate(proofs):
+        raw = bytes(p.proof_bytes if isinstance(p, ProofArtifact) else p)  # read in place: no copy of a bytes object
+        keep.append(raw)
+        refs[i].bytes, refs[i].len = C.cast(C.c_char_p(raw), C.c_void_p).value, len(raw)
+        if roots[i] is not None:
+            if len(roots[i]) != 32:
+                raise SezkpError(-1, "manifest_root must be 32 bytes")
+            rb = bytes(roots[i])
+            keep.append(rb)
+            refs[i].manifest_root = C.cast(C.c_char_p(rb), C.c_void_p).value
+        refs[i].tau = int(taus[i] or 0)
+    err = C.create_string_buffer(1024)
+    check(call(refs, n, out, err, 1024), err)
+    return [VerifyResult(o.code == 0, int(o.code), o.msg.decode(errors="replace")) for o in out]
+
+
 def _head(major: int, v: int) -> bytes:
     if v < 24:
         return bytes([(major << 5) | v])
@@ -167,6 +202,14 @@ class StarkV1:
         rc = lib.sezkp_stark_v1_verify(artifact.proof_bytes, len(artifact.proof_bytes), C.byref(blocks.view()),
                                        bytes(manifest_root), err, 1024)
         check(rc, err)
+
+    @staticmethod
+    def verify_batch(proofs, manifest_roots=None, taus=None) -> list:
+        """Verify a batch of proofs on device 0 (sezkp_stark_v1_verify_batch):
+        one VerifyResult per proof. `proofs`: bytes or ProofArtifacts;
+        manifest_roots: per proof 32 bytes or None; taus: per proof, 0 = not
+        checked."""
+        return _verify_batch(lib.sezkp_stark_v1_verify_batch, proofs, manifest_roots, taus)
 
     @staticmethod
     def air_audit(blocks: BlockSoA, bitmaps: bool = False) -> AirAudit:
@@ -241,6 +284,34 @@ class ProverContext:
         err = C.create_string_buffer(1024)
         check(lib.sezkp_ctx_air_audit(self._h, C.byref(a), vb, rb, err, 1024), err)
         return AirAudit._from_c(a, vb.raw if bitmaps else None, rb.raw if bitmaps else None)
+
+    def verify_batch(self, proofs, manifest_roots=None, taus=None) -> list:
+        """Verify a batch of proofs with the Merkle chains hashed on this
+        context's device (sezkp_ctx_verify_batch): one VerifyResult per proof,
+        equal to the host verifier's verdict. Needs no uploaded trace."""
+        return _verify_batch(lambda *a: lib.sezkp_ctx_verify_batch(self._h, *a), proofs, manifest_roots, taus)
+
+    def verify(self, artifact: ProofArtifact, blocks: BlockSoA, manifest_root: bytes) -> None:
+        """StarkV1.verify with the hashing on this context's device: same
+        checks in the same order, same SezkpError."""
+        if artifact.backend != "stark":
+            raise SezkpError(-5, "backend kind mismatch: expected STARK")
+        if bytes(artifact.manifest_root) != bytes(manifest_root):
+            raise SezkpError(-5, "manifest root mismatch")
+        blocks.check_shape()
+        if blocks.n_blocks and blocks.tau == 0:
+            # sezkp_proof_ref cannot ask for a tau of 0 to be checked (0 = unchecked): the host verifier can
+            return StarkV1.verify(artifact, blocks, manifest_root)
+        # the host call checks tau only for a non-empty block list
+        r = self.verify_batch([artifact.proof_bytes], [bytes(manifest_root)], [blocks.tau if blocks.n_blocks else 0])[0]
+        if not r.ok:
+            raise SezkpError(r.code, r.message)
+
+    def verify_times(self) -> dict:
+        """Where the last verify_batch spent its time (sezkp_ctx_verify_times)."""
+        buf = (C.c_double * len(VERIFY_TIMES))()
+        n = lib.sezkp_ctx_verify_times(self._h, buf, len(VERIFY_TIMES))
+        return {VERIFY_TIMES[i]: buf[i] for i in range(n)}
 
     def prove_view(self, manifest_root: bytes) -> memoryview:
         """The proof bytes as a read-only view of the context's pinned host
