@@ -700,10 +700,9 @@ __global__ void __launch_bounds__(256) k_runroots_scatter_multi(const RunRootsBa
 // One 64-lane workgroup per (layer, index): recompute the 64-leaf group that
 // holds the index (levels < lstore), then read stored siblings above.
 __global__ void __launch_bounds__(64) k_fri_paths(const FriLayerDev* __restrict__ layers, const uint32_t* __restrict__ req,
-                                                  const uint32_t* __restrict__ count, ProofLayout P) {
+                                                  ProofLayout P) {
   __shared__ uint32_t lds[8][64];
   const int lane = threadIdx.x;
-  if (count && blockIdx.x >= *count) return;  // grid sized for the most requests a rank can own
   const uint32_t r = req[3 * blockIdx.x];
   const uint64_t idx = req[3 * blockIdx.x + 1];
   const uint32_t ord = req[3 * blockIdx.x + 2];  // q*2k + 2r + side
@@ -933,37 +932,6 @@ hipError_t launch_upper_jobs(hipStream_t st, const UpperJob* d_jobs, int njobs) 
   return hipGetLastError();
 }
 
-void plan_upper_jobs(const TreeDev& T, int from, std::vector<std::vector<UpperJob>>& passes, int to,
-                     const uint32_t* gath, uint64_t nrun, int logP) {
-  const int top = (to > 0 && to < T.logLen) ? to : T.logLen;
-  if (gath && from == top) {  // a one-node cap (P = 1): the job copies the gathered root into it
-    if (passes.empty()) passes.resize(1);
-    UpperJob J{T, from, 0u, to, 0};
-    J.gath = gath;
-    J.nrun = nrun;
-    J.logP = logP;
-    passes[0].push_back(J);
-    return;
-  }
-  int p = 0;
-  while (from < top) {
-    const int c = top - from;
-    const int step = c < 10 ? c : 10;
-    if ((int)passes.size() <= p) passes.resize(p + 1);
-    for (uint64_t w = 0; w < (1ULL << (T.logLen - from - step)); w++) {
-      UpperJob J{T, from, (uint32_t)w, to, 0};
-      if (p == 0 && gath) {  // the first pass reads the gathered run roots (and stores them)
-        J.gath = gath;
-        J.nrun = nrun;
-        J.logP = logP;
-      }
-      passes[p].push_back(J);
-    }
-    from += step;
-    p++;
-  }
-}
-
 hipError_t launch_tree_upper(hipStream_t st, TreeDev* trees, int ntrees, uint64_t tree_stride_nodes,
                              uint64_t root_stride_words, int from_level) {
   const TreeDev T = trees[0];
@@ -986,10 +954,10 @@ hipError_t launch_tree_upper(hipStream_t st, TreeDev* trees, int ntrees, uint64_
 }
 
 hipError_t launch_fri_paths(hipStream_t st, const FriLayerDev* d_layers, const uint32_t* d_req, int nreq,
-                            const ProofLayout& P, const uint32_t* d_count) {
+                            const ProofLayout& P) {
   if (nreq == 0) return hipSuccess;
   if ((uint64_t)nreq > (uint64_t)P.nq * 2 * P.k) return hipErrorInvalidValue;
-  hipLaunchKernelGGL(k_fri_paths, dim3(nreq), dim3(64), 0, st, d_layers, d_req, d_count, P);
+  hipLaunchKernelGGL(k_fri_paths, dim3(nreq), dim3(64), 0, st, d_layers, d_req, P);
   return hipGetLastError();
 }
 

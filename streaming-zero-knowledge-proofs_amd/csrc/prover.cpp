@@ -26,6 +26,7 @@
 #include "codec.h"
 #include "comm.h"
 #include "host_crypto.h"
+#include "prove_plan.h"
 #include "sezkp_internal.h"
 #include "verify_plan.h"
 
@@ -33,8 +34,6 @@ using namespace sezkp;
 
 namespace {
 
-constexpr int NUM_QUERIES = 30;  // params.rs:31
-constexpr int BLOWUP_LOG2 = 3;   // params.rs:28
 // ST_L0TREE brackets exactly one launch (k_layer16 over the LDE) so bench.py
 // can quote that kernel's live duration; ST_L0UP holds its upper levels.
 enum Stage { ST_EXPAND, ST_COMMIT, ST_OUTER, ST_COMPOSE, ST_INTT, ST_LDE, ST_DEEP, ST_L0TREE, ST_L0UP, ST_FRI,
@@ -95,43 +94,11 @@ const NttTables& tables_for_device(int dev) {
   return g_tabs.emplace(dev, t).first->second.T;
 }
 
-const char* KIND_NAME[7] = {"mv", "wflag", "wsym", "head", "winlen", "in_off", "out_off"};
-
-std::string label_of(int c, uint32_t tau) {  // all_labels (openings.rs:89-116)
-  if (c == 0) return "input_mv";
-  if (c == 1) return "is_first";
-  if (c == 2) return "is_last";
-  return std::string(KIND_NAME[(c - 3) / tau]) + "_" + std::to_string((c - 3) % tau);
-}
-
-ColTemplate make_template(int c, uint32_t tau, const std::string& label) {
-  ColTemplate t{};
-  uint8_t b[64] = {0};
-  memcpy(b, "col_leaf", 8);
-  const uint32_t L = (uint32_t)label.size();
-  for (int i = 0; i < 4; i++) b[8 + i] = (uint8_t)(L >> (8 * i));
-  memcpy(b + 12, label.data(), L);
-  for (int i = 0; i < 16; i++)
-    t.words[i] = (uint32_t)b[4 * i] | (uint32_t)b[4 * i + 1] << 8 | (uint32_t)b[4 * i + 2] << 16 |
-                 (uint32_t)b[4 * i + 3] << 24;
-  t.off = 12 + L;
-  t.block_len = 20 + L;
-  if (c < 3) { t.kind = c; t.tape = 0; }
-  else { t.kind = 3 + (c - 3) / tau; t.tape = (c - 3) % tau; }
-  return t;
-}
-
 uint64_t rd64(const uint8_t* p) {
   uint64_t x = 0;
   for (int i = 7; i >= 0; i--) x = (x << 8) | p[i];
   return x;
 }
-int ilog2(uint64_t x) {
-  int l = 0;
-  while ((1ULL << l) < x) l++;
-  return l;
-}
-
 }  // namespace
 
 // ======================================================================== ctx
@@ -576,26 +543,6 @@ static void fail_point(int rank, const char* name) {
 }
 
 
-// The column chunks [ch_lo, ch_hi) rank g of 2^logP commits (all of them on
-// one device) and the blocks holding their rows [ch_lo * 1024, ch_hi * 1024]
-// (the extra row: compose and the next_* openings read row i + 1; the last
-// row's wrap to row 0 is never read: row n - 1 is a block's last row, where
-// the head-update term vanishes, and its next_* openings belong to rank 0).
-static void shard_range(const uint64_t* step_start, uint32_t nblk, int logn, int rank, int logP, uint64_t& ch_lo,
-                        uint64_t& ch_hi, uint32_t& blk_lo, uint32_t& blk_cnt) {
-  const uint64_t n = 1ULL << logn;
-  const int logChunks = logn > COL_CHUNK_LOG2 ? logn - COL_CHUNK_LOG2 : 0;
-  const uint64_t nchunks = 1ULL << logChunks, chunk_rows = n < 1024 ? n : 1024;
-  ch_lo = (nchunks >> logP) * (uint64_t)rank;
-  ch_hi = ch_lo + (nchunks >> logP);
-  const uint64_t r0 = ch_lo * chunk_rows, r1 = std::min<uint64_t>(ch_hi * chunk_rows, n - 1);
-  auto block_of = [&](uint64_t row) {
-    return (uint32_t)(std::upper_bound(step_start, step_start + nblk + 1, row) - step_start - 1);
-  };
-  blk_lo = block_of(r0);
-  blk_cnt = block_of(r1) - blk_lo + 1;
-}
-
 // Blocks of zero steps (step_hi = step_lo - 1, so step_hi - step_lo + 1 wraps
 // to 0) contribute no rows: TraceColumns::build and RowIter skip them
 // (columns.rs:254-257,281-284; openings.rs:209-238) and nothing else of
@@ -675,12 +622,15 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   free_all(true);
   tau = v.tau;
   nblk = v.n_blocks;
-  // rows: sum over blocks of (step_hi - step_lo + 1) (columns.rs:254-257)
-  uint64_t rows = 0;
   // the kernels index the step arrays through step_start: it must start at 0
   // and every block must hold step_hi - step_lo + 1 >= 1 steps (no wrap-around;
-  // the blocks of zero steps, whose range wraps to 0, are gone already)
-  if (nblk && v.step_start[0] != 0) throw Err{SEZKP_E_INVALID, "step_start[0] must be 0"};
+  // the blocks of zero steps, whose range wraps to 0, are gone already); the
+  // rows are then step_start[nblk] (columns.rs:254-257)
+  try {
+    plan_require_start0(v.step_start, nblk);
+  } catch (const PlanError& e) {
+    throw Err{SEZKP_E_INVALID, e.msg};
+  }
   for (uint32_t k = 0; k < nblk; k++) {
     if (v.step_hi[k] < v.step_lo[k] || v.step_hi[k] - v.step_lo[k] >= (1ULL << 28))
       throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step range [" + std::to_string(v.step_lo[k]) +
@@ -690,18 +640,44 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     if (len != steps)
       throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step_hi-step_lo+1=" + std::to_string(len) +
                                      " but movement_log has " + std::to_string(steps) + " steps"};
-    rows += len;
   }
-  if (rows == 0 || (rows & (rows - 1)) != 0)
-    throw Err{SEZKP_E_INVALID, "n_base must be a power of two (got " + std::to_string(rows) + ")"};  // lde.rs:51
-  if (rows > (1ULL << 28)) throw Err{SEZKP_E_INVALID, "trace too long for one device (n > 2^28)"};
-  n = rows;
+  // ---- plan (prove_plan.h): every size and offset below, no device call
+  ShapePlan sp;
+  ColumnPlan cp;
+  FriPlan fp;
+  ProofPlan pp;
+  try {
+    sp = plan_shape(tau, v.step_start, nblk, rank, logP, sharded());
+    cp = plan_columns(sp, v.step_start, getenv("SEZKP_NO_DICT") == nullptr);  // read per upload
+    fp = plan_fri(sp);
+    pp = plan_proof(sp, cp.labels);
+  } catch (const PlanError& e) {
+    throw Err{SEZKP_E_INVALID, e.msg};
+  }
+  n = sp.n;
   if (audit_n != n) free_audit();
-  logn = ilog2(n);
-  logN = logn + BLOWUP_LOG2;
-  N = 1ULL << logN;
-  ncols = 3 + 7 * (int)tau;
-  logChunks = logn > COL_CHUNK_LOG2 ? logn - COL_CHUNK_LOG2 : 0;
+  logn = sp.logn;
+  logN = sp.logN;
+  N = sp.N;
+  ncols = sp.ncols;
+  logChunks = sp.logChunks;
+  ch_lo = sp.ch_lo;
+  ch_hi = sp.ch_hi;
+  blk_lo = sp.blk_lo;
+  blk_cnt = sp.blk_cnt;
+  full_lde = sp.full_lde;
+  M = sp.M;
+  logM = sp.logM;
+  tree_wg_log = sp.tree_wg_log;
+  rR = sp.rR;
+  if (nrows == ~0ull) nrows = n - row0;
+  {  // the rows this context reads: every row (one device) or the whole blocks over its chunks (+ the halo row)
+    const uint64_t need0 = v.step_start[blk_lo], need1 = v.step_start[blk_lo + blk_cnt];
+    if (row0 > need0 || row0 + nrows < need1 || row0 + nrows > n)
+      throw Err{SEZKP_E_INVALID, "step arrays hold rows [" + std::to_string(row0) + ", " + std::to_string(row0 + nrows) +
+                                     ") but this context needs rows [" + std::to_string(need0) + ", " +
+                                     std::to_string(need1) + ")"};
+  }
 
   // ---- trace image (tape-major): the step arrays go over as the view holds
   // them (row-major [n][tau]) and are transposed on the device
@@ -716,25 +692,9 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     slot[1].ready = keep;
   }
   alloc_slot(slot[0]);
-  const uint64_t nchunks = 1ULL << logChunks, chunk_rows = n < 1024 ? n : 1024;
-  // sharded: this rank commits chunks [ch_lo, ch_hi) of every column
-  if (sharded()) {
-    if (logn < 12 + logP || logP > 3)
-      throw Err{SEZKP_E_INVALID, "sharded proving needs n >= 4096 * P rows and P <= 8 (n = " + std::to_string(n) +
-                                     ", P = " + std::to_string(world) + ")"};
-  }
-  shard_range(v.step_start, nblk, logn, sharded() ? rank : 0, sharded() ? logP : 0, ch_lo, ch_hi, blk_lo, blk_cnt);
   uint64_t* d_bs = dalloc<uint64_t>(nblk + 1);
   up(d_bs, v.step_start, nblk + 1);
   cur_step_start.assign(v.step_start, v.step_start + nblk + 1);
-  if (nrows == ~0ull) nrows = n - row0;
-  {  // the rows this context reads: every row (one device) or the whole blocks over its chunks (+ the halo row)
-    const uint64_t need0 = v.step_start[blk_lo], need1 = v.step_start[blk_lo + blk_cnt];
-    if (row0 > need0 || row0 + nrows < need1 || row0 + nrows > n)
-      throw Err{SEZKP_E_INVALID, "step arrays hold rows [" + std::to_string(row0) + ", " + std::to_string(row0 + nrows) +
-                                     ") but this context needs rows [" + std::to_string(need0) + ", " +
-                                     std::to_string(need1) + ")"};
-  }
   write_trace(slot[0], v, st, row0, nrows);
   HIP_OR_THROW(hipStreamSynchronize(st));
   TraceSlot& t0 = slot[0];
@@ -754,65 +714,11 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   T.head = dalloc<int32_t>((size_t)tau * n + 2);
   T.head_rng = dalloc<int64_t>(2 * (size_t)tau * nblk + 2);
 
-  // ---- column templates + outer trees (all levels kept)
-  labels.clear();
-  std::vector<ColTemplate> tm;
-  for (int c = 0; c < ncols; c++) {
-    labels.push_back(label_of(c, tau));
-    if (labels.back().size() > 44) throw Err{SEZKP_E_INVALID, "column label too long"};
-    tm.push_back(make_template(c, tau, labels.back()));
-  }
-  // per-column tables: leaf tables for small raw domains (i8/u8: 256, u16:
-  // 65536 entries) and uniform-subtree tables U_0..U_10 for piecewise columns
-  uint64_t tab_nodes = 0;
-  std::vector<uint32_t> tab_cols, pw_cols;
-  std::vector<DictCol> dcols;
-  const bool use_dict = n >= (1ULL << COL_CHUNK_LOG2) && getenv("SEZKP_NO_DICT") == nullptr;
-  tab_units = 0;
-  for (int c = 0; c < ncols; c++) {
-    ColTemplate& t = tm[c];
-    t.tab = NO_TAB;
-    t.tab_log = 0;
-    if (use_dict && kind_dict(t.kind)) {
-      dcols.push_back(DictCol{(uint32_t)c, NO_DICT, (uint64_t)dcols.size() * DICT_LEVELS * DICT_CAP});
-    } else if (kind_has_leaf_table(t.kind)) {
-      t.tab_log = t.kind == 5 ? 16 : 8;
-      t.tab = tab_nodes;
-      tab_nodes += 1ULL << t.tab_log;
-      tab_units = std::max<uint64_t>(tab_units, 1ULL << t.tab_log);
-      tab_cols.push_back(c);
-    } else if (kind_piecewise(t.kind)) {
-      const uint64_t units = (t.kind == 1 || t.kind == 2) ? 2 : nblk;
-      t.tab = tab_nodes;
-      tab_nodes += units * U_LEVELS;
-      tab_units = std::max<uint64_t>(tab_units, units);
-      tab_cols.push_back(c);
-      pw_cols.push_back(c);
-    }
-  }
-  // chunks whose rows cross few block boundaries go to the piecewise kernel;
-  // the rest (many short blocks) are committed densely for every column
-  std::vector<uint32_t> work, pw_chunks;
-  std::vector<uint8_t> dense_chunk(nchunks, 0);
-  {
-    uint32_t k = 0;
-    for (uint64_t ch = 0; ch < nchunks; ch++) {
-      const uint64_t c0 = ch * chunk_rows, c1 = c0 + chunk_rows;
-      while (k < nblk && v.step_start[k] <= c0) k++;
-      int inside = 0;
-      for (uint32_t j = k; j < nblk && v.step_start[j] < c1; j++)
-        if (j == 0 || v.step_start[j] != v.step_start[j - 1]) inside++;
-      if (ch < ch_lo || ch >= ch_hi) continue;
-      if (inside <= 16) pw_chunks.push_back((uint32_t)ch);
-      else dense_chunk[ch] = 1;
-    }
-  }
-  for (int c = 0; c < ncols; c++) {
-    if (use_dict && kind_dict(tm[c].kind)) continue;
-    const bool pw = kind_piecewise(tm[c].kind);
-    for (uint64_t ch = ch_lo; ch < ch_hi; ch++)
-      if (!pw || dense_chunk[ch]) { work.push_back((uint32_t)c); work.push_back((uint32_t)ch); }
-  }
+  // ---- column templates, tables and work lists (ColumnPlan)
+  labels = cp.labels;
+  const std::vector<ColTemplate>& tm = cp.tmpl;
+  const std::vector<DictCol>& dcols = cp.dcols;
+  tab_units = cp.tab_units;
   d_tmpl = dalloc<ColTemplate>(ncols);
   up(d_tmpl, tm.data(), tm.size());
   // column roots, then the guard words ([0] this rank's guard, [8 + r] rank
@@ -822,14 +728,10 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   d_err = d_colroots + (size_t)ncols * 8;
   d_dstatus = d_err + 16;
   HIP_OR_THROW(hipMemset(d_err, 0, 64));
-  d_tabs = dalloc<uint32_t>(tab_nodes * 8 + 8);
-  n_tab_cols = (int)tab_cols.size();
-  d_tab_cols = dalloc<uint32_t>(tab_cols.size() + 1);
-  up(d_tab_cols, tab_cols.data(), tab_cols.size());
-  for (DictCol& h : dcols)  // head columns: the same tape's mv column (delta plan)
-    if (tm[h.col].kind == 6)
-      for (size_t i = 0; i < dcols.size(); i++)
-        if (tm[dcols[i].col].kind == 3 && tm[dcols[i].col].tape == tm[h.col].tape) h.mv = (uint32_t)i;
+  d_tabs = dalloc<uint32_t>(cp.tab_nodes * 8 + 8);
+  n_tab_cols = (int)cp.tab_cols.size();
+  d_tab_cols = dalloc<uint32_t>(cp.tab_cols.size() + 1);
+  up(d_tab_cols, cp.tab_cols.data(), cp.tab_cols.size());
   n_dict = (int)dcols.size();
   have_plans = false;
   dict_info.assign(dcols.size(), sezkp_dict_plan_info{});
@@ -870,26 +772,22 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     }
   }
   d_dlev = dalloc<uint32_t>(dcols.size() * (n >> COL_CHUNK_LOG2) * DLEV_NODES * 8 + 8);
-  dict_of.assign(ncols, NO_DICT);
-  for (size_t i = 0; i < dcols.size(); i++) dict_of[dcols[i].col] = (uint32_t)i;
-  n_pw_cols = (int)pw_cols.size();
-  d_pw_cols = dalloc<uint32_t>(pw_cols.size() + 1);
-  up(d_pw_cols, pw_cols.data(), pw_cols.size());
-  n_pw_chunks = (int)pw_chunks.size();
-  d_pw_chunks = dalloc<uint32_t>(pw_chunks.size() + 1);
-  up(d_pw_chunks, pw_chunks.data(), pw_chunks.size());
-  n_work = (int)(work.size() / 2);
-  d_work = dalloc<uint32_t>(work.size() + 2);
-  up(d_work, work.data(), work.size());
+  dict_of = cp.dict_of;
+  n_pw_cols = (int)cp.pw_cols.size();
+  d_pw_cols = dalloc<uint32_t>(cp.pw_cols.size() + 1);
+  up(d_pw_cols, cp.pw_cols.data(), cp.pw_cols.size());
+  n_pw_chunks = (int)cp.pw_chunks.size();
+  d_pw_chunks = dalloc<uint32_t>(cp.pw_chunks.size() + 1);
+  up(d_pw_chunks, cp.pw_chunks.data(), cp.pw_chunks.size());
+  n_work = (int)(cp.work.size() / 2);
+  d_work = dalloc<uint32_t>(cp.work.size() + 2);
+  up(d_work, cp.work.data(), cp.work.size());
   outer_stride = tree_stored_nodes(logChunks, 0);
   d_outer = dalloc<uint32_t>((size_t)ncols * outer_stride * 8);
 
-  // ---- LDE / FRI workspace
-  // Layer r has 2^(k-r) leaves. Run layers (r <= rR, >= 4096 P leaves) are
-  // held as this rank's runs of 4096 (all of it when P = 1); the remaining
-  // small layers are replicated on every rank.
+  // ---- LDE / FRI workspace (FriPlan): the buffers, then every layer's
+  // values, trees and roots as base + offset
   const int k = logN;
-  const uint64_t S = 1ULL << L16_LOG;
   d_base = dalloc<uint64_t>(n);
   Tm.hr = dalloc<uint64_t>(n);
   Tm.sl = dalloc<uint64_t>(n);
@@ -900,7 +798,6 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   Tm.bl = dalloc<uint64_t>((size_t)nblk + 1);
   Tm.row_flags = T.row_flags;
   Tm.row_blk = T.row_blk;
-  full_lde = sharded() && world == 2;
   {  // DEEP quotient tables (sized for this rank's M = N / P LDE points, or N)
     const uint64_t Ml = full_lde ? N : N >> logP;
     d_dq_part = dalloc<uint64_t>(n / 1024 + 1);  // partials of >= 1024 rows (dq_rows_per_part)
@@ -908,178 +805,76 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     d_dq_rhi = dalloc<uint64_t>(Ml > 4096 ? Ml >> 12 : 1);
     d_dq_rhk = dalloc<uint64_t>(n > 4096 ? n >> 12 : 1);
   }
-  M = N >> logP;
-  logM = logN - logP;
-  // tree workgroups of 2048 leaves (1024 on small per-device LDEs): alone a
-  // 4096-leaf workgroup is as fast, but with proofs in flight the half-size
-  // ones let the concurrent proofs' kernels interleave (+5% in flight, round 5,
-  // profiles/r05/ab/tree_wg2048_headline_ab.txt)
-  tree_wg_log = M <= (1ULL << 21) ? L16S_LOG : L16M_LOG;
-  rR = sharded() ? k - L16_LOG - logP : (k >= L16_LOG ? k - L16_LOG : -1);
-  d_lde = dalloc<uint64_t>(M);
+  d_lde = dalloc<uint64_t>(fp.lde_vals);
   if (sharded()) {
     d_cyc = dalloc<uint64_t>(full_lde ? N : M);
     if (!full_lde) d_xbuf = dalloc<uint64_t>(M);
   }
+  d_fri = dalloc<uint64_t>(fp.run_vals + 1);
+  d_rep = dalloc<uint64_t>(fp.rep_vals + 1);
+  d_roots = dalloc<uint32_t>((size_t)fp.root_slots * 8);
+  uint32_t* d_nodes = dalloc<uint32_t>(fp.total_nodes * 8 + 8);
   lvals.assign(k + 1, nullptr);
   ltrees.assign(k + 1, TreeDev{});
   caps.assign(k + 1, TreeDev{});
   rr_gather.assign(k + 1, nullptr);
-  uint64_t run_vals = 0, rep_vals = sharded() ? (S << logP) : 0;
-  for (int r = 1; r <= k; r++) {
-    if (r <= rR) run_vals += (N >> r) >> logP;
-    else rep_vals += N >> r;
-  }
-  d_fri = dalloc<uint64_t>(run_vals + 1);
-  d_rep = dalloc<uint64_t>(rep_vals + 1);
-  d_roots = dalloc<uint32_t>((size_t)(k + 2) * 8);
-  uint32_t* root_dummy = d_roots + 8 * (k + 1);
-  uint64_t total_nodes = 0;
-  for (int r = 0; r <= k; r++) {
-    const int ll = r <= rR ? k - r - logP : k - r;
-    total_nodes += tree_stored_nodes(ll, LSTORE_FRI);
-    if (sharded() && r <= rR) total_nodes += tree_stored_nodes(k - r, L16_LOG) + ((N >> r) >> L16_LOG);
-  }
-  uint32_t* d_nodes = dalloc<uint32_t>(total_nodes * 8 + 8);
-  uint64_t off = 0, voff = 0, roff = sharded() ? (S << logP) : 0;
   std::vector<FriLayerDev> ly(k + 1);
+  uint64_t* const val_buf[3] = {d_lde, d_fri, d_rep};
   for (int r = 0; r <= k; r++) {
-    const bool run = r <= rR;
-    if (r == 0) lvals[r] = d_lde;
-    else if (run) { lvals[r] = d_fri + voff; voff += (N >> r) >> logP; }
-    else { lvals[r] = d_rep + roff; roff += N >> r; }
-    TreeDev& t = ltrees[r];
-    t.nodes = d_nodes + off * 8;
-    t.logLen = run ? k - r - logP : k - r;
-    t.lstore = LSTORE_FRI;
-    t.root = (run && sharded()) ? root_dummy : d_roots + 8 * r;
-    off += tree_stored_nodes(t.logLen, LSTORE_FRI);
-    caps[r] = t;
-    if (run && sharded()) {
-      TreeDev& c = caps[r];
-      c.nodes = d_nodes + off * 8;
-      c.logLen = k - r;
-      c.lstore = L16_LOG;
-      c.root = d_roots + 8 * r;
-      off += tree_stored_nodes(k - r, L16_LOG);
-      rr_gather[r] = d_nodes + off * 8;
-      off += (N >> r) >> L16_LOG;
-    }
-    ly[r] = FriLayerDev{lvals[r], ltrees[r], caps[r], (uint32_t)(run && sharded()), (uint32_t)logP};
+    const FriLayerPlan& L = fp.layers[r];
+    lvals[r] = val_buf[L.buf] + L.val_off;
+    ltrees[r] = TreeDev{d_nodes + L.node_off * 8, d_roots + 8 * L.root_slot, L.logLen, L.lstore};
+    caps[r] = TreeDev{d_nodes + L.cap_off * 8, d_roots + 8 * L.cap_root_slot, L.cap_logLen, L.cap_lstore};
+    if (L.has_cap) rr_gather[r] = d_nodes + L.gather_off * 8;
+    ly[r] = FriLayerDev{lvals[r], ltrees[r], caps[r], (uint32_t)L.has_cap, (uint32_t)logP};
   }
   d_layers = dalloc<FriLayerDev>(k + 1);
   up(d_layers, ly.data(), ly.size());
-  // replicated layers of >= 4096 leaves (P > 1), then the small-layer tail
-  rep16.clear();
-  tail_first = rR + 1 > 1 ? rR + 1 : 1;
-  while (tail_first <= k && k - tail_first >= L16_LOG) rep16.push_back(tail_first++);
-  // forest of the run layers 1..rR (local runs of 4096 leaves per WG) and,
-  // sharded, of the replicated layers of >= 4096 leaves (whole subtrees of
-  // 4096, level 12 and up from the upper jobs): their WGs run beside the run
-  // layers' instead of as three serial few-WG launches after them, and come
-  // first in the grid (each is one WG's 4096-leaf chain: started last, they
-  // would set the launch's end)
+  rep16 = fp.rep16;
+  tail_first = fp.tail_first;
   {
     std::vector<ForestLayer> fl;
-    uint32_t wgs = 0;
-    for (int r : rep16) {
-      fl.push_back(ForestLayer{lvals[r], ltrees[r], wgs, (uint32_t)std::min(L16_LOG, tree_wg_log)});
-      wgs += (uint32_t)(1ULL << (ltrees[r].logLen - tree_wg_log));
-    }
-    for (int r = 1; r <= rR; r++) {
-      fl.push_back(ForestLayer{lvals[r], ltrees[r], wgs, (uint32_t)wg_stop()});
-      wgs += (uint32_t)(1ULL << (ltrees[r].logLen - tree_wg_log));
-    }
+    for (const ForestEntryPlan& e : fp.forest) fl.push_back(ForestLayer{lvals[e.layer], ltrees[e.layer], e.wg_start, e.stop});
     n_forest = (int)fl.size();
-    forest_wgs = wgs;
+    forest_wgs = fp.forest_wgs;
     d_forest = dalloc<ForestLayer>(fl.size() + 1);
     if (!fl.empty()) up(d_forest, fl.data(), fl.size());
-    d_tailbuf = sharded() ? nullptr : dalloc<uint64_t>((size_t)TAIL_MAX << TAIL_MAX);
+    d_tailbuf = fp.tailbuf ? dalloc<uint64_t>((size_t)TAIL_MAX << TAIL_MAX) : nullptr;
   }
-  // upper levels (> 12): layer 0's cap, then every other cap / replicated tree
-  {
-    std::vector<std::vector<UpperJob>> p0, pF, pL0, pLR;
-    // run layers start from the level their layer16 WGs stopped at
-    const int from = tree_stop();
-    // sharded: a run layer's cap starts from its allgathered run roots (the
-    // first pass permutes them into cap order itself: no scatter launch)
-    auto gath_of = [&](int r) -> const uint32_t* { return sharded() && r <= rR ? rr_gather[r] : nullptr; };
-    auto nrun_of = [&](int r) -> uint64_t { return sharded() ? (N >> r) >> (L16_LOG + logP) : 0; };
-    if (rR >= 0 && (caps[0].logLen > from || gath_of(0)))
-      plan_upper_jobs(caps[0], from, p0, 0, gath_of(0), nrun_of(0), logP);
-    const int rep_from = std::min(L16_LOG, tree_wg_log);
-    for (int r = 1; r <= k; r++) {
-      const bool runl = r <= rR;
-      if ((runl || std::find(rep16.begin(), rep16.end(), r) != rep16.end()) &&
-          (caps[r].logLen > (runl ? from : rep_from) || (runl && gath_of(r))))
-        plan_upper_jobs(caps[r], runl ? from : rep_from, pF, 0, runl ? gath_of(r) : nullptr, nrun_of(r), logP);
+  {  // upper-level jobs: the planned jobs with their layer's tree and gathered roots bound
+    std::vector<UpperJob> all = fp.jobs;
+    for (size_t i = 0; i < all.size(); i++) {
+      const int r = fp.job_layer[i];
+      all[i].tree = fp.job_cap[i] ? caps[r] : ltrees[r];
+      if (all[i].gath) all[i].gath = rr_gather[r];
     }
-    // sharded with 1024-leaf WGs: the run trees' levels 11..12 (the run roots
-    // the caps are gathered from) by upper jobs before each allgather
-    if (sharded() && wg_stop() < L16_LOG && rR >= 0) {
-      plan_upper_jobs(ltrees[0], wg_stop(), pL0, L16_LOG);
-      for (int r = 1; r <= rR; r++) plan_upper_jobs(ltrees[r], wg_stop(), pLR, L16_LOG);
-    }
-    std::vector<UpperJob> all;
-    jobs0.clear();
-    jobsF.clear();
-    jobsL0.clear();
-    jobsLR.clear();
-    auto add = [&](std::vector<std::vector<UpperJob>>& ps, std::vector<std::pair<size_t, int>>& out) {
-      for (auto& v : ps) { out.push_back({all.size(), (int)v.size()}); all.insert(all.end(), v.begin(), v.end()); }
-    };
-    add(p0, jobs0);
-    add(pF, jobsF);
-    add(pL0, jobsL0);
-    add(pLR, jobsLR);
+    jobs0 = fp.jobs0;
+    jobsF = fp.jobsF;
+    jobsL0 = fp.jobsL0;
+    jobsLR = fp.jobsLR;
     d_jobs = dalloc<UpperJob>(all.size() + 1);
     if (!all.empty()) up(d_jobs, all.data(), all.size());
   }
-  max_fri_req = (size_t)NUM_QUERIES * 2 * k;
-  max_open_req = (size_t)NUM_QUERIES * (3 + 9 * tau);
+  max_fri_req = pp.max_fri_req;
+  max_open_req = pp.max_open_req;
   // The query requests (a few KB per proof) live in mapped host memory that
   // the path / opening kernels read directly, so no small H2D copy queues
   // behind a staged trace upload on the copy engine (round 3,
   // tools/ab_req_mapped.sh: host -> proof 7.91 -> 7.97e9, mean of three)
   h_req = hmapped<uint32_t>(max_fri_req * 3 + max_open_req * OPEN_REQ_WORDS);
   d_req = h_req;
-  // ---- proof layout (proof.rs:80-98, bincode fixint LE)
-  {
-    BinWriter w;
-    w.u64(N);
-    w.u64(tau);
-    w.u64((uint64_t)ncols);
-    root_pos.assign(ncols, 0);
-    for (int c = 0; c < ncols; c++) {
-      w.u64(labels[c].size());
-      w.raw(labels[c].data(), labels[c].size());
-      root_pos[c] = w.b.size();
-      w.raw(std::string(32, '\0').data(), 32);
-    }
-    hdr_bytes = w.b.size();
-    PL = ProofLayout{};
-    PL.open_per_q = 9 * tau + 3;
-    PL.nq = NUM_QUERIES;
-    PL.k = k;
-    PL.tau = tau;
-    PL.open_bytes = 80 + 32 * (uint64_t)logn;  // path_in_chunk + path_to_chunk = log2(n) levels
-    PL.q_bytes = 16 + PL.open_per_q * PL.open_bytes;
-    PL.fr_off = 8 + NUM_QUERIES * PL.q_bytes;
-    PL.fq_off = PL.fr_off + 8 + 32 * (uint64_t)(k + 1);
-    PL.fq_bytes = 8 + 8 * (uint64_t)(k + 1) + 8;
-    for (int r = 0; r < k; r++) PL.fq_bytes += 2 * (16 + 32 * (uint64_t)(k - r));
-    PL.tail_off = PL.fq_off + 8 + NUM_QUERIES * PL.fq_bytes;
-    PL.total = PL.tail_off + 8 + 32;
-    PL.base = dalloc<uint32_t>(PL.total / 4 + 2);
-    h_proof = halloc<uint8_t>(hdr_bytes + PL.total);
-    memcpy(h_proof, w.b.data(), hdr_bytes);
-  }
+  // ---- proof image (ProofPlan): the header's bytes, the body's layout
+  hdr_bytes = pp.hdr_bytes;
+  root_pos = pp.root_pos;
+  PL = pp.PL;
+  PL.base = dalloc<uint32_t>(PL.total / 4 + 2);
+  h_proof = halloc<uint8_t>(hdr_bytes + PL.total);
+  memcpy(h_proof, pp.header.data(), hdr_bytes);
   h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + 2 * (size_t)n_dict);
   d_chal = dalloc<DevChal>(1);
   h_chal = halloc<DevChal>(1);
   d_dict_of = dalloc<uint32_t>((size_t)ncols);
   up(d_dict_of, dict_of.data(), dict_of.size());
-  if (k > FS_MAX_BETAS) throw Err{SEZKP_E_INVALID, "LDE domain too large for the challenge record"};
   release_spares();
   loaded = true;
 }
@@ -1444,6 +1239,87 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
   vfy_ms[SEZKP_VT_WALL] = ms_since(t_call);
 }
 
+// The knobs of a proof, read from the environment in this one place. Each
+// keeps the moment it has always been read at; tests set several of them
+// between the proofs of one process, so the per-proof ones must stay so.
+//   once per process:  SEZKP_HOST_TRACE, SEZKP_SYNC_DEBUG, SEZKP_DEBUG_STALL_AFTER
+//                      (here), SEZKP_TEST_WORKER_DELAY_US (worker_delay_us),
+//                      SEZKP_COLL_TIMEOUT_S (coll_timeout_s), SEZKP_DEBUG_FAIL_AT
+//                      (fail_point)
+//   per proof:         everything else below
+//   elsewhere:         SEZKP_NO_DICT per upload (upload), SEZKP_FORCE_SHARDED per
+//                      context (ctx_create), SEZKP_VERIFY_CHUNK_BYTES per verify
+//                      call (verify_batch)
+struct ProveOptions {
+  bool host_trace = false;   // SEZKP_HOST_TRACE=1: host-side marks printed per proof
+  bool sync_debug = false;   // SEZKP_SYNC_DEBUG: sync after every launch, to name the failing kernel
+  const char* stall_after = nullptr;  // SEZKP_DEBUG_STALL_AFTER=<rank>:<collective> (prove_body, coll)
+  bool kernel_events = false;  // SEZKP_KERNEL_EVENTS=1: an event pair around the FRI forest launch
+  // Per-stage timed events only on request (SEZKP_STAGE_EVENTS=1, or with the
+  // kernel events): each timed event record costs the stream ~3.5 us, so the
+  // 13 of a proof added ~45 us to one proof at a time (round 4,
+  // profiles/r04/stage_events_ab.txt); without them the device stage times
+  // read 0
+  bool stage_events = false;
+  bool no_deep_poly = false;   // SEZKP_NO_DEEP_POLY: the per-point DEEP division
+  uint32_t dict_tab_cap = DICT_CAP;  // largest dictionary table above level 0 (entries; SEZKP_DICT_TAB_CAP, for A/Bs)
+  // test hook: plan the dictionary columns as on a device with 2^v rows
+  // (SEZKP_TEST_DICT_PLAN_ROWS_LOG=<v>), so small traces run the level / lane
+  // forms that only 2^21 rows and more select; below 10 (unset: -1) = off
+  long dict_plan_rows_log = -1;
+  bool dict_cache_off = false;  // SEZKP_DICT_CACHE=0: every column rebuilt
+  bool dist_intt = false;       // SEZKP_DIST_INTT=1: the distributed INTT (sharded, P > 1)
+  // test hook: SEZKP_DEBUG_TRIP_GUARD=<rank> sets that rank's guard word, to
+  // check that the failure is collective (tests/test_gpu_sharded.py; a good, a
+  // tripped and a good proof in one process, tests/test_gpu_dict_cache.py)
+  bool trip_guard = false;
+  int trip_guard_rank = 0;
+
+  static ProveOptions read() {
+    static const bool htrace = getenv("SEZKP_HOST_TRACE") != nullptr;
+    static const bool sync_debug = getenv("SEZKP_SYNC_DEBUG") != nullptr;
+    static const char* stall = getenv("SEZKP_DEBUG_STALL_AFTER");
+    auto on = [](const char* name) {
+      const char* e = getenv(name);
+      return e && atoi(e) != 0;
+    };
+    ProveOptions o;
+    o.host_trace = htrace;
+    o.sync_debug = sync_debug;
+    o.stall_after = stall;
+    o.kernel_events = on("SEZKP_KERNEL_EVENTS");
+    o.stage_events = o.kernel_events || on("SEZKP_STAGE_EVENTS");
+    o.no_deep_poly = getenv("SEZKP_NO_DEEP_POLY") != nullptr;
+    if (const char* cap = getenv("SEZKP_DICT_TAB_CAP")) {
+      const long v = atol(cap);
+      if (v >= 1 && v <= (long)DICT_CAP) o.dict_tab_cap = (uint32_t)v;
+    }
+    if (const char* pr = getenv("SEZKP_TEST_DICT_PLAN_ROWS_LOG")) o.dict_plan_rows_log = atol(pr);
+    const char* dce = getenv("SEZKP_DICT_CACHE");
+    o.dict_cache_off = dce && atoi(dce) == 0;
+    o.dist_intt = on("SEZKP_DIST_INTT");
+    if (const char* trip = getenv("SEZKP_DEBUG_TRIP_GUARD")) {
+      o.trip_guard = true;
+      o.trip_guard_rank = atoi(trip);
+    }
+    return o;
+  }
+  // the rows the dictionary planner prices for (0: the real ones)
+  uint64_t dict_plan_rows(uint64_t nrows) const {
+    long v = dict_plan_rows_log;
+    // a device with 2^v rows plans up to 2^(6 + a) rows per lane, a =
+    // v - 20 (0..2), and production then has at least 2^(14 + a) rows per
+    // device: every 256-lane commit workgroup is full. Keep the hook inside
+    // that space: with fewer real rows v is lowered until a full workgroup
+    // fits (a partly filled workgroup at a > 0 is a form nothing plans)
+    int lg = 0;
+    while ((2ULL << lg) <= nrows) lg++;
+    const long v_max = lg >= 16 ? 40 : 20 + (lg > 14 ? lg - 14 : 0);
+    if (v > v_max) v = v_max;
+    return v >= COL_CHUNK_LOG2 && v <= 40 ? 1ULL << v : 0;
+  }
+};
+
 size_t sezkp_ctx::prove(const uint8_t mroot[32]) {
   if (broken)
     throw Err{SEZKP_E_DEVICE, "context unusable: an earlier prove aborted the communicator after a failure past "
@@ -1479,9 +1355,10 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   using clk = std::chrono::steady_clock;
   const auto t_enter = clk::now();
   double t_sync = 0, t_last = 0;
-  // SEZKP_HOST_TRACE=1: host-side marks (us from entry) printed per proof, to
-  // split the Fiat-Shamir round trips into wake-up, host work and launch
-  static const bool htrace = getenv("SEZKP_HOST_TRACE") != nullptr;
+  const ProveOptions opt = ProveOptions::read();
+  // host-side marks (us from entry) printed per proof, to split the
+  // Fiat-Shamir round trips into wake-up, host work and launch
+  const bool htrace = opt.host_trace;
   std::vector<std::pair<const char*, double>> hmarks;
   auto mark = [&](const char* what) {
     if (htrace) hmarks.push_back({what, std::chrono::duration<double, std::micro>(clk::now() - t_enter).count()});
@@ -1503,15 +1380,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   };
   HIP_OR_THROW(hipSetDevice(device));
   const int k = logN;
-  const char* kev_env = getenv("SEZKP_KERNEL_EVENTS");
-  const bool kprobe = kev_env && atoi(kev_env) != 0;
-  // Per-stage timed events only on request (SEZKP_STAGE_EVENTS=1, or with the
-  // kernel events): each timed event record costs the stream ~3.5 us, so the
-  // 13 of a proof added ~45 us to one proof at a time (round 4,
-  // profiles/r04/stage_events_ab.txt); without them the device stage times
-  // read 0
-  const char* sev_env = getenv("SEZKP_STAGE_EVENTS");
-  const bool stage_ev = kprobe || (sev_env && atoi(sev_env) != 0);
+  const bool kprobe = opt.kernel_events, stage_ev = opt.stage_events;
   auto rec = [&](int s) {
     if (stage_ev) HIP_OR_THROW(hipEventRecord(ev[s], st));
   };
@@ -1521,10 +1390,14 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     HIP_OR_THROW(hipEventRecord(kev[end ? 1 : 0], st));
     if (end) kdone = true;
   };
-  static const bool sync_debug = getenv("SEZKP_SYNC_DEBUG") != nullptr;  // name the failing kernel
   auto ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess && sync_debug) e = hipStreamSynchronize(st);
+    if (e == hipSuccess && opt.sync_debug) e = hipStreamSynchronize(st);
     if (e != hipSuccess) throw Err{SEZKP_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e)};
+  };
+  // "record on A, wait on B": stream `to` goes on after what `from` holds now
+  auto fork = [&](hipStream_t from, hipStream_t to, hipEvent_t e) {
+    HIP_OR_THROW(hipEventRecord(e, from));
+    HIP_OR_THROW(hipStreamWaitEvent(to, e, 0));
   };
 
   const bool sharded = this->sharded();
@@ -1555,8 +1428,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // test hook: SEZKP_DEBUG_STALL_AFTER=<rank>:<collective> holds that rank's
     // stream after the collective (a wait on a mapped word released only at
     // destroy), so the next wait must give up at SEZKP_COLL_TIMEOUT_S
-    static const char* stall = getenv("SEZKP_DEBUG_STALL_AFTER");
-    if (hook_match(stall, rank, name)) {
+    if (hook_match(opt.stall_after, rank, name)) {
       if (!stall_word) {
         HIP_OR_THROW(hipHostMalloc(&stall_word, 64, hipHostMallocMapped | hipHostMallocCoherent));
         *stall_word = 0;
@@ -1567,30 +1439,9 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   const uint64_t P1 = (uint64_t)world - 1;
   const uint64_t row_lo = n >= 1024 ? ch_lo << COL_CHUNK_LOG2 : 0;
   const uint64_t row_hi = n >= 1024 ? ch_hi << COL_CHUNK_LOG2 : n;
-  const bool no_deep_poly = getenv("SEZKP_NO_DEEP_POLY") != nullptr;
-  // largest dictionary table above level 0 (entries; SEZKP_DICT_TAB_CAP, for A/Bs)
-  uint32_t dict_tab_cap = DICT_CAP;
-  if (const char* cap = getenv("SEZKP_DICT_TAB_CAP")) {
-    const long v = atol(cap);
-    if (v >= 1 && v <= (long)DICT_CAP) dict_tab_cap = (uint32_t)v;
-  }
-  // test hook: plan the dictionary columns as on a device with 2^v rows
-  // (SEZKP_TEST_DICT_PLAN_ROWS_LOG=<v>; read per prove), so small traces run
-  // the level / lane forms that only 2^21 rows and more select
-  uint64_t dict_plan_rows = 0;
-  if (const char* pr = getenv("SEZKP_TEST_DICT_PLAN_ROWS_LOG")) {
-    long v = atol(pr);
-    // a device with 2^v rows plans up to 2^(6 + a) rows per lane, a =
-    // v - 20 (0..2), and production then has at least 2^(14 + a) rows per
-    // device: every 256-lane commit workgroup is full. Keep the hook inside
-    // that space: with fewer real rows v is lowered until a full workgroup
-    // fits (a partly filled workgroup at a > 0 is a form nothing plans)
-    int lg = 0;
-    while ((2ULL << lg) <= row_hi - row_lo) lg++;
-    const long v_max = lg >= 16 ? 40 : 20 + (lg > 14 ? lg - 14 : 0);
-    if (v > v_max) v = v_max;
-    if (v >= COL_CHUNK_LOG2 && v <= 40) dict_plan_rows = 1ULL << v;
-  }
+  const bool no_deep_poly = opt.no_deep_poly;
+  const uint32_t dict_tab_cap = opt.dict_tab_cap;
+  const uint64_t dict_plan_rows = opt.dict_plan_rows(row_hi - row_lo);
   // ---- dictionary table reuse (DictCache): the epoch moves with every
   // host-side input of make_plan and dict_entry (the upload moves it for the
   // templates, the DictCols and the table buffers), after a proof on this
@@ -1598,8 +1449,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   // run), and on every proof with SEZKP_DICT_CACHE=0 (read per prove), so that
   // every column is rebuilt
   {
-    const char* dce = getenv("SEZKP_DICT_CACHE");
-    const bool cache_off = dce && atoi(dce) == 0;
+    const bool cache_off = opt.dict_cache_off;
     DictHostKey hk;
     hk.n = n;
     hk.nrows = row_hi - row_lo;
@@ -1666,7 +1516,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   // distributed}_detail.json: two
   // collectives fewer outweigh (P - 1)/P of a 2^21-point INTT; P = 8 1.204
   // -> 1.132 ms predicted), so it is the default.
-  const bool dist_intt = sharded && world > 1 && getenv("SEZKP_DIST_INTT") && atoi(getenv("SEZKP_DIST_INTT")) != 0;
+  const bool dist_intt = sharded && world > 1 && opt.dist_intt;
   DeepPoly dpoly{d_dq_rlo, d_dq_rhi, d_dq_rhk};
   std::vector<uint8_t> roots((size_t)(k + 1) * 32);
   uint64_t rows[NUM_QUERIES], frows[NUM_QUERIES];
@@ -1691,8 +1541,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // (VALU-bound) dictionary columns; disjoint outer-tree leaves. (Starting
     // them later, beside part of the dictionary chain only, or on a CU-masked
     // stream, measured even or slower in round 3.)
-    HIP_OR_THROW(hipEventRecord(ev_expand, st));
-    HIP_OR_THROW(hipStreamWaitEvent(st2, ev_expand, 0));
+    fork(st, st2, ev_expand);
     ok(launch_col_tables(st2, T, d_tmpl, d_tab_cols, n_tab_cols, tab_units, d_tabs, blk_lo, blk_cnt), "col_tables");
     ok(launch_col_commit(st2, T, d_tmpl, d_work, n_work, d_tabs, d_outer, outer_stride), "col_commit");
     ok(launch_col_commit_pw(st2, T, d_tmpl, d_pw_cols, n_pw_cols, d_pw_chunks, n_pw_chunks, d_tabs, d_outer,
@@ -1708,12 +1557,8 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
                           row_hi - row_lo, d_dlev, dcache, dict_tab_cap, dict_plan_rows),
        "col_commit_dict");
     HIP_OR_THROW(hipStreamWaitEvent(st, ev_cols, 0));
-    // test hook: SEZKP_DEBUG_TRIP_GUARD=<rank> sets that rank's guard word, to
-    // check that the failure is collective (tests/test_gpu_sharded.py)
-    // (read per prove: a good, a tripped and a good proof in one process,
-    // tests/test_gpu_dict_cache.py)
-    const char* trip = getenv("SEZKP_DEBUG_TRIP_GUARD");
-    if (trip && atoi(trip) == rank) HIP_OR_THROW(hipMemsetAsync(d_err, 0x7f, 1, st));
+    // test hook (ProveOptions::trip_guard)
+    if (opt.trip_guard && opt.trip_guard_rank == rank) HIP_OR_THROW(hipMemsetAsync(d_err, 0x7f, 1, st));
     if (sharded) {
       // the chunk roots of every column and every rank's guard word in one
       // group: sharded ranks see all guard words, so a trip on any rank makes
@@ -1866,8 +1711,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       // kappa r^(4096t) power tables: a latency-bound ~10 us) on the side
       // stream beside the INTT, which does not read them
       if (dq) {
-        HIP_OR_THROW(hipEventRecord(ev_qin, st));
-        HIP_OR_THROW(hipStreamWaitEvent(st2, ev_qin, 0));
+        fork(st, st2, ev_qin);
         ok(launch_q_tables(st2, d_dq_part, logn, full_lde ? logN : logM, d_chal, d_dq_rlo, d_dq_rhi, d_dq_rhk, dq_per),
            "q_tables");
         HIP_OR_THROW(hipEventRecord(ev_qout, st2));
@@ -1956,8 +1800,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     auto launch_tail = [&](const uint64_t* src_vals) {
       if (tail_first > k) return;
       const TailArgs ta = tail_args(src_vals);
-      HIP_OR_THROW(hipEventRecord(ev_fold, st));
-      HIP_OR_THROW(hipStreamWaitEvent(st2, ev_fold, 0));
+      fork(st, st2, ev_fold);
       ok(launch_fri_tail(st2, ta), "fri_tail");
       HIP_OR_THROW(hipEventRecord(ev_tail, st2));
     };
@@ -1966,19 +1809,24 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // fold chain, up to FOLD_MAX layers per pass (2 measured even); the forest
     // follows the whole chain (hashing the first pass's layers beside the later
     // folds measured slower in round 3: the forest starves the folds)
-    for (int r = 0; r < rR;) {
-      const int F = std::min(FOLD_MAX, rR - r);
-      if (F >= 2) {
-        FoldOuts fo{};
-        fo.beta = dbeta + r;
-        for (int m = 1; m <= F; m++) fo.out[m - 1] = lvals[r + m];
-        ok(launch_foldm(st, lvals[r], fo, F, ltrees[r + F].logLen), "fri_foldm");
+    // layers r_from + 1 .. r_to from first_src (the values of layer r_from)
+    auto fold_chain = [&](const uint64_t* first_src, int r_from, int r_to, const char* label_multi,
+                          const char* label_single) {
+      for (int r = r_from; r < r_to;) {
+        const int F = std::min(FOLD_MAX, r_to - r);
+        const uint64_t* src = r == r_from ? first_src : lvals[r];
+        if (F >= 2) {
+          FoldOuts fo{};
+          fo.beta = dbeta + r;
+          for (int m = 1; m <= F; m++) fo.out[m - 1] = lvals[r + m];
+          ok(launch_foldm(st, src, fo, F, ltrees[r + F].logLen), label_multi);
+        } else {
+          ok(launch_fold(st, src, lvals[r + 1], ltrees[r + 1].logLen, 0, dbeta + r), label_single);
+        }
         r += F;
-      } else {
-        ok(launch_fold(st, lvals[r], lvals[r + 1], ltrees[r + 1].logLen, 0, dbeta + r), "fri_fold");
-        r += 1;
       }
-    }
+    };
+    fold_chain(lvals[0], 0, rR, "fri_foldm", "fri_fold");
     const uint64_t* rep_src = rR >= 0 ? lvals[rR] : d_lde;  // full values of the layer above the replicated ones
     // single device: the small layers ride in the forest launch's first
     // workgroups (sharded: their own kernel on the side stream)
@@ -1995,20 +1843,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       // pass, the tail (side stream) and one forest of run + replicated layers
       coll("fri_rep_values", P1 * S * 8, [&] { comm->allgather(lvals[rR], d_rep, (size_t)S * 8, st); });
       rep_src = d_rep;
-      const int last = rR + (int)rep16.size();
-      for (int r = rR; r < last;) {
-        const int F = std::min(FOLD_MAX, last - r);
-        const uint64_t* src = r == rR ? d_rep : lvals[r];
-        if (F >= 2) {
-          FoldOuts fo{};
-          fo.beta = dbeta + r;
-          for (int m = 1; m <= F; m++) fo.out[m - 1] = lvals[r + m];
-          ok(launch_foldm(st, src, fo, F, ltrees[r + F].logLen), "fri_rep_folds");
-        } else {
-          ok(launch_fold(st, src, lvals[r + 1], ltrees[r + 1].logLen, 0, dbeta + r), "fri_rep_fold");
-        }
-        r += F;
-      }
+      fold_chain(d_rep, rR, rR + (int)rep16.size(), "fri_rep_folds", "fri_rep_fold");
       if (!rep16.empty()) rep_src = lvals[rep16.back()];
       // (the tail launched after the forest instead measured even, round 6)
       launch_tail(rep_src);
@@ -2031,7 +1866,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     if (tail_first <= k && !tail_merged) HIP_OR_THROW(hipStreamWaitEvent(st, ev_tail, 0));
     rec(ST_FRI + 1);
     // ---- FRI roots -> query rows mod n and mod N (prover.rs:248, 297), the
-    // path / opening requests each rank owns and (device mode) the body fields
+    // path / opening requests each rank owns
     if (sharded) HIP_OR_THROW(hipMemsetAsync(PL.base, 0, PL.total, st));  // one writer per byte
     HIP_OR_THROW(hipMemcpyAsync(h_small, d_roots, (size_t)(k + 1) * 32, hipMemcpyDeviceToHost, st));
   };
@@ -2103,7 +1938,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       push_open(0, row);  // input_mv
     }
   };
-  auto enqueue_D = [&](size_t nf_grid, size_t no_grid, const uint32_t* cnt_f, const uint32_t* cnt_o) {
+  auto enqueue_D = [&](size_t nf_grid, size_t no_grid) {
     mark("req_copy");
     const uint32_t* req = d_req;
     // the openings and the FRI paths write disjoint sections of the proof image
@@ -2111,11 +1946,10 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // stream beside the path kernel, and (single device) their section (~70% of
     // the proof) goes back over PCIe from there while the paths still run
     mark("col_open");
-    HIP_OR_THROW(hipEventRecord(ev_fold, st));
-    HIP_OR_THROW(hipStreamWaitEvent(st2, ev_fold, 0));
+    fork(st, st2, ev_fold);
     if (stage_ev) HIP_OR_THROW(hipEventRecord(oev[0], st2));
     ok(launch_col_open(st2, T, d_tmpl, d_outer, outer_stride, logChunks, req + 3 * max_fri_req, (int)no_grid, PL,
-                       d_tabs, d_dlev, d_dplans, d_dtabs, d_dcols, cnt_o),
+                       d_tabs, d_dlev, d_dplans, d_dtabs, d_dcols),
        "col_open");
     if (stage_ev) HIP_OR_THROW(hipEventRecord(oev[1], st2));
     rec(ST_OPEN + 1);
@@ -2123,7 +1957,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     if (!sharded) HIP_OR_THROW(hipMemcpyAsync(h_proof + hdr_bytes, PL.base, PL.fr_off, hipMemcpyDeviceToHost, st2));
     HIP_OR_THROW(hipEventRecord(ev_tail, st2));
     mark("open_d2h_issued");
-    ok(launch_fri_paths(st, d_layers, req, (int)nf_grid, PL, cnt_f), "fri_paths");
+    ok(launch_fri_paths(st, d_layers, req, (int)nf_grid, PL), "fri_paths");
     mark("fri_paths_issued");
     if (sharded) {
       HIP_OR_THROW(hipStreamWaitEvent(st, ev_tail, 0));  // the openings are part of the byte-sum
@@ -2151,7 +1985,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   sync();
   mark("sync3");
   host_3();
-  enqueue_D(nf, no, nullptr, nullptr);
+  enqueue_D(nf, no);
   sync();
   mark("sync4");
   if (htrace) {
@@ -2217,6 +2051,29 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
 }
 
 // ==================================================================== C ABI
+// Runs an entry point's body: SEZKP_OK, or an Err's code and message, or
+// `other` with the message of any other exception (SEZKP_E_NOMEM everywhere
+// but sezkp_ctx_dist_ntt).
+template <class F>
+static int32_t guarded(char* err, size_t err_len, int32_t other, F&& body) {
+  try {
+    body();
+    return SEZKP_OK;
+  } catch (const Err& e) {
+    set_err(err, err_len, e.msg);
+    return e.code;
+  } catch (const std::exception& e) {
+    set_err(err, err_len, e.what());
+    return other;
+  }
+}
+// every entry point that uses the context's streams or buffers but
+// sezkp_ctx_stage (which fills the other slot while a proof runs) and
+// sezkp_ctx_prove_async (which checks under the slot's mutex)
+static void require_idle(sezkp_ctx* ctx) {
+  if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+}
+
 extern "C" {
 
 uint32_t sezkp_abi_version(void) { return SEZKP_ABI_VERSION; }
@@ -2318,17 +2175,10 @@ int32_t sezkp_comm_unique_id(uint8_t out[128], char* err, size_t err_len) {
 void sezkp_ctx_destroy(sezkp_ctx* ctx) { delete ctx; }
 
 int32_t sezkp_ctx_stage(sezkp_ctx* ctx, const sezkp_block_view* blocks, char* err, size_t err_len) {
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !blocks) throw Err{SEZKP_E_INVALID, "null argument"};
     ctx->stage(*blocks);
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 int32_t sezkp_host_register(void* p, size_t bytes) {
   if (!p || !bytes) return SEZKP_E_INVALID;
@@ -2340,34 +2190,20 @@ int32_t sezkp_host_unregister(void* p) {
 }
 
 int32_t sezkp_ctx_upload(sezkp_ctx* ctx, const sezkp_block_view* blocks, char* err, size_t err_len) {
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !blocks) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    require_idle(ctx);
     ctx->upload(*blocks);
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 
 int32_t sezkp_ctx_upload_rows(sezkp_ctx* ctx, const sezkp_block_view* blocks, uint64_t row0, uint64_t nrows,
                               char* err, size_t err_len) {
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !blocks) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    require_idle(ctx);
     ctx->upload(*blocks, row0, nrows);
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 int32_t sezkp_shard_rows(const uint64_t* step_start, uint32_t n_blocks, int32_t rank, int32_t world, uint64_t* row0,
                          uint64_t* nrows) {
@@ -2389,39 +2225,25 @@ int32_t sezkp_shard_rows(const uint64_t* step_start, uint32_t n_blocks, int32_t 
 int32_t sezkp_ctx_prove(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, sezkp_buf* proof_bytes,
                         char* err, size_t err_len) {
   (void)flags;
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !manifest_root || !proof_bytes) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    require_idle(ctx);
     ctx->take_staged();
     const size_t len = ctx->prove(manifest_root);
     proof_bytes->data = (uint8_t*)malloc(len ? len : 1);
     if (!proof_bytes->data) throw Err{SEZKP_E_NOMEM, "out of host memory"};
     memcpy(proof_bytes->data, ctx->h_proof, len);
     proof_bytes->len = len;
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 
 int32_t sezkp_ctx_air_audit(sezkp_ctx* ctx, sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits,
                             char* err, size_t err_len) {
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !out) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    require_idle(ctx);
     ctx->air_audit(out, violating_bits, rejectable_bits);
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 
 static bool verify_batch_args_ok(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out, char* err,
@@ -2440,19 +2262,15 @@ static bool verify_batch_args_ok(const sezkp_proof_ref* proofs, uint32_t n, sezk
 
 int32_t sezkp_ctx_verify_batch(sezkp_ctx* ctx, const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out,
                                char* err, size_t err_len) {
-  try {
-    if (!ctx) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (!verify_batch_args_ok(proofs, n, out, err, err_len)) return SEZKP_E_INVALID;
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
-    ctx->verify_batch(proofs, n, out);
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
+  if (!ctx) {
+    set_err(err, err_len, "null argument");
+    return SEZKP_E_INVALID;
   }
+  if (!verify_batch_args_ok(proofs, n, out, err, err_len)) return SEZKP_E_INVALID;
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    require_idle(ctx);
+    ctx->verify_batch(proofs, n, out);
+  });
 }
 
 int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max) {
@@ -2465,26 +2283,19 @@ int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max
 int32_t sezkp_ctx_prove_borrow(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, const uint8_t** data,
                                size_t* len, char* err, size_t err_len) {
   (void)flags;
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !manifest_root || !data || !len) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    require_idle(ctx);
     ctx->take_staged();
     *len = ctx->prove(manifest_root);
     *data = ctx->h_proof;
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 
 int32_t sezkp_ctx_prove_async(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, char* err,
                               size_t err_len) {
   (void)flags;
-  try {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !manifest_root) throw Err{SEZKP_E_INVALID, "null argument"};
     if (!ctx->loaded) throw Err{SEZKP_E_INVALID, "context has no trace: call sezkp_ctx_upload first"};
     if (!ctx->async) {
@@ -2502,14 +2313,7 @@ int32_t sezkp_ctx_prove_async(sezkp_ctx* ctx, const uint8_t manifest_root[32], u
       a.state = AsyncSlot::RUNNING;
     }
     a.cv.notify_all();
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_NOMEM;
-  }
+  });
 }
 
 int32_t sezkp_ctx_wait(sezkp_ctx* ctx, const uint8_t** data, size_t* len, char* err, size_t err_len) {
@@ -2606,9 +2410,10 @@ int32_t sezkp_ctx_comm_stats(const sezkp_ctx* ctx, sezkp_comm_stat* out, int32_t
 // rank needs no send image: the transform is bit-reversed in place.
 int32_t sezkp_ctx_dist_ntt(sezkp_ctx* ctx, uint64_t* local, uint64_t* scratch, uint32_t log_n, int32_t dir,
                            char* err, size_t err_len) {
-  try {
+  // any exception that is no Err is the communicator's here: SEZKP_E_DEVICE, on purpose
+  return guarded(err, err_len, SEZKP_E_DEVICE, [&] {
     if (!ctx || !local || !scratch) throw Err{SEZKP_E_INVALID, "null argument"};
-    if (ctx->busy()) throw Err{SEZKP_E_INVALID, "a proof is in flight on this context (call sezkp_ctx_wait)"};
+    require_idle(ctx);
     if (ctx->broken) throw Err{SEZKP_E_DEVICE, "context unusable after an aborted collective"};
     if (dir != 1 && dir != -1) throw Err{SEZKP_E_INVALID, "dir must be +1 or -1"};
     const int P = ctx->world, logP = ctx->logP;
@@ -2647,14 +2452,7 @@ int32_t sezkp_ctx_dist_ntt(sezkp_ctx* ctx, uint64_t* local, uint64_t* scratch, u
       ok(dntt_permute_twiddle(st, scratch, local, logM, ctx->tw, e_step, true, true, inv_n), "dist_ntt twiddle");
       ok(ntt_dit(st, local, logM, true, ctx->tw, nullptr, 0, 1), "dist_ntt local");
     }
-    return SEZKP_OK;
-  } catch (const Err& e) {
-    set_err(err, err_len, e.msg);
-    return e.code;
-  } catch (const std::exception& e) {
-    set_err(err, err_len, e.what());
-    return SEZKP_E_DEVICE;
-  }
+  });
 }
 
 static std::vector<MetaEntry> meta_for(uint64_t domain_n, uint32_t tau, uint32_t flags) {

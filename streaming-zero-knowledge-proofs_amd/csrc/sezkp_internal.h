@@ -7,6 +7,8 @@
 
 #include <vector>
 
+#include "plan_types.h"
+
 namespace sezkp {
 
 struct DevChal;        // transcript-derived values in device memory (below)
@@ -116,23 +118,6 @@ hipError_t dntt_dft(hipStream_t st, uint64_t* r, int P, uint64_t Q, bool inverse
 hipError_t bintt_dft_twiddle(hipStream_t st, uint64_t* r, int P, uint64_t Q, uint32_t d, int logn,
                              const NttTables& T);
 
-// A binary Merkle tree over 2^logLen leaves whose levels >= lstore are kept
-// in HBM: level l (lstore <= l <= logLen) starts at node
-// off(l) = 2^(logLen-lstore+1) - 2^(logLen-l+1); 8 u32 words per node.
-// Lower levels are recomputed from the leaf values when a path is opened.
-struct TreeDev {
-  uint32_t* nodes;
-  uint32_t* root;   // 8 words
-  int logLen;
-  int lstore;
-};
-__host__ __device__ inline uint64_t tree_level_off(int logLen, int lstore, int l) {
-  return (1ULL << (logLen - lstore + 1)) - (1ULL << (logLen - l + 1));
-}
-__host__ __device__ inline uint64_t tree_stored_nodes(int logLen, int lstore) {
-  return logLen >= lstore ? (1ULL << (logLen - lstore + 1)) - 1 : 0;
-}
-
 // Device image of the trace (struct-of-arrays, tape-major), built by upload.
 struct TraceDev {
   uint64_t n;
@@ -207,36 +192,7 @@ struct Alphas {
       slack_reconstruct, sym_bits_bool, sym_reconstruct, boundary_first, boundary_last;
 };
 
-// Per-column BLAKE3 message template for labelled leaves
-// BLAKE3("col_leaf" || u32 len || label || v LE)  (merkle.rs:132-147).
-struct ColTemplate {
-  uint32_t words[16];
-  uint32_t block_len;  // 20 + len(label)
-  uint32_t kind;       // 0 input_mv,1 is_first,2 is_last,3+k: per-tape kind k
-  uint32_t tape;
-  uint32_t off;        // byte offset of the value = 12 + len(label)
-  uint64_t tab;        // node offset of this column's leaf/uniform table, or NO_TAB
-  uint32_t tab_log;    // leaf table: log2(entries) (8 or 16); 0 otherwise
-  uint32_t pad;
-};
-constexpr uint64_t NO_TAB = ~0ULL;
-constexpr int U_LEVELS = 11;  // uniform-subtree hashes U_0..U_10 (chunk = 2^10 rows)
-
-// Column kinds whose leaf depends on a small raw domain (i8 / u8 / u16):
-// leaves come from a per-column table of all possible labelled leaves.
-__host__ __device__ inline bool kind_has_leaf_table(uint32_t kind) { return kind == 0 || kind == 3 || kind == 4 || kind == 5; }
-// Columns that are piecewise constant along the trace (per-block constants and
-// the block-boundary flags): committed from uniform-subtree hashes.
-__host__ __device__ inline bool kind_piecewise(uint32_t kind) { return kind == 1 || kind == 2 || kind >= 7; }
-
-// Dictionary (memoized subtree) commitment of dense small-range columns.
-constexpr int DICT_LEVELS = 5;          // tables T_0..T_4
-constexpr uint32_t DICT_CAP = 65536;    // entries per table level
-struct DictCol {
-  uint32_t col;
-  uint32_t mv;   // head columns: dictionary index of the same tape's mv column (delta plan), else NO_DICT
-  uint64_t tab;  // node offset of this column's DICT_LEVELS x DICT_CAP tables
-};
+// Dictionary (memoized subtree) commitment of dense small-range columns: DictCol, DICT_* in plan_types.h.
 struct DictPlan {
   int64_t min;
   uint32_t R;    // range size (codes = raw - min < R)
@@ -271,44 +227,13 @@ struct DictCache {
 // TD[c0 + R (d1 + dR d2 + dR^2 d3)] = H(T_1[c0 + R c1], T_1[c2 + R c3]) with
 // c_j = c_{j-1} + mv_j (codes). Groups with a block start at g+1..g+3 use
 // the two T_1 nodes directly. Needs R^2 <= DICT_CAP and R dR^3 <= DICT_CAP.
-__host__ __device__ inline bool kind_dict(uint32_t kind) { return kind == 0 || (kind >= 3 && kind <= 6); }
-// Chunk levels 6..9 of every dictionary column (16 + 8 + 4 + 2 nodes per
-// 1024-row chunk), written by the commitment, read by the openings.
-constexpr int DICT_LANE_LOG = 6;  // rows per lane of the dictionary commitment (level-6 nodes)
-constexpr int DLEV_NODES = 30;
 __host__ __device__ inline int dlev_base(int level) { return level == 6 ? 0 : level == 7 ? 16 : level == 8 ? 24 : 28; }
-constexpr uint32_t NO_DICT = 0xFFFFFFFFu;
 // extra lane rows (log2) of the dictionary commitment for table level K:
 // high K leaves few table nodes per 64 rows, so lanes take 2^(6+a) rows
 __host__ __device__ inline int dict_extra(int K) { return K >= 3 ? 2 : (K == 2 ? 1 : 0); }
-constexpr int OPEN_REQ_WORDS = 5;  // column, row lo, row hi, ordinal, dictionary index
-
-constexpr int LSTORE_FRI = 6;
-constexpr int COL_CHUNK_LOG2 = 10;
-// Device image of the bincode ProofV1 body (proof.rs:80-98) after the
-// column-root header: every record there is 8-byte aligned and fixed-size,
-// so the opening and path kernels write proof bytes in place.
-//   0                 u64 #queries
-//   8 + q*q_bytes     u64 row, u64 tau, then open_per_q openings of open_bytes
-//   fr_off            u64 k+1, (k+1) x 32 B FRI roots            (host)
-//   fq_off            u64 #queries
-//   fq_off+8+q*fq_bytes  u64 k+1, k+1 positions, u64 k, 2k path records
-//   tail_off          final value (8 B), manifest root (32 B)     (root: host)
-struct ProofLayout {
-  uint32_t* base;          // device pointer, 8-byte aligned
-  uint64_t open_bytes;     // 80 + 32*log2(n)
-  uint64_t q_bytes;        // 16 + open_per_q * open_bytes
-  uint64_t fr_off, fq_off, fq_bytes, tail_off, total;
-  uint32_t open_per_q;     // 9*tau + 3
-  uint32_t nq;             // queries (params.rs:31)
-  int k;                   // log2(N)
-  uint32_t tau;
-};
-
 // ------------------------------------------------- Fiat-Shamir challenges
 // The transcript-derived values every challenge-dependent kernel reads from
 // device memory, written by the host transcript (one H2D copy per point).
-constexpr int FS_MAX_BETAS = 64;
 struct DevChal {
   uint64_t alpha[8];                // derive_alphas (params.rs:82-92); reuse of prover.rs:86-98 in the kernels
   uint64_t mask[4];                 // derive_mask_coeffs (masking.rs:56-79)
@@ -373,7 +298,7 @@ struct VerifyJobDev;
 struct VerifyLabel;
 hipError_t launch_verify_chains(hipStream_t st, const uint8_t* bytes, const VerifyJobDev* jobs, const uint8_t* roots,
                                 const VerifyLabel* labels, uint32_t njobs, uint32_t* result);
-// Sharded LDE layout change (see prover.cpp, prove_sharded): cyclic coset
+// Sharded LDE layout change (prover.cpp, enqueue_B): cyclic coset
 // values of rank g (index g + P*j) <-> runs of S = 2^12 consecutive indices.
 hipError_t launch_cyc_pack(hipStream_t st, const uint64_t* cyc, uint64_t* send, uint64_t M, int logP);
 hipError_t launch_cyc_unpack(hipStream_t st, const uint64_t* recv, uint64_t* local, uint64_t M, int logP);
@@ -408,29 +333,8 @@ struct FriLayerDev {
   uint32_t sharded;
   uint32_t logP;
 };
-// Upper-level reduction job: one WG reduces <= 1024 stored nodes of `tree`
-// from level `from` (WG index wg within that level).
-struct UpperJob {
-  TreeDev tree;
-  int from;
-  uint32_t wg;
-  int to;  // last level to build (0: up to the root)
-  uint32_t pad;
-  // sharded cap of a run layer: level `from` (12) comes from the allgathered
-  // run roots (rank-major: rank d's nrun roots at [d nrun, (d + 1) nrun)),
-  // cap node g = root g >> logP of rank g & (P - 1); the job stores it too
-  const uint32_t* gath = nullptr;
-  uint64_t nrun = 0;
-  int logP = 0;
-  int pad2 = 0;
-};
-void plan_upper_jobs(const TreeDev& T, int from, std::vector<std::vector<UpperJob>>& passes, int to = 0,
-                     const uint32_t* gath = nullptr, uint64_t nrun = 0, int logP = 0);
 hipError_t launch_upper_jobs(hipStream_t st, const UpperJob* d_jobs, int njobs);
 
-constexpr int L16_LOG = 12;  // leaves per WG of the 16-leaves-per-lane layer kernel
-constexpr int L16S_LOG = 10; // leaves per WG of its 4-leaves-per-lane form (small trees)
-constexpr int L16M_LOG = 11; // leaves per WG of its 8-leaves-per-lane form
 // stop: highest level the WG reduces to (L16_LOG = its run root; LSTORE_FRI
 // leaves levels 7..12 to the upper jobs, whose lanes are all busy)
 // wg_log: leaves per WG (L16_LOG, or L16S_LOG for trees too small to fill
@@ -456,7 +360,6 @@ struct ForestLayer {
 
 // Small FRI layers (logLen <= Ls <= 11) in one launch; layer Ls - j is
 // folded from layer Ls - j + 1 with beta[j]; src = layer Ls + 1.
-constexpr int TAIL_MAX = 12;
 struct TailArgs {
   const uint64_t* src;
   int Ls;
@@ -471,14 +374,12 @@ hipError_t launch_forest16(hipStream_t st, const ForestLayer* d_layers, int nlay
                            const TailArgs* tail = nullptr, uint64_t* tailbuf = nullptr, uint32_t wg_base = 0,
                            int wg_log = L16_LOG);
 // requests: (layer, index, ordinal in the proof's FRI records) triples
-// d_count != null: the number of requests is read on the device (grid = nreq, the most possible)
 hipError_t launch_fri_paths(hipStream_t st, const FriLayerDev* d_layers, const uint32_t* d_req, int nreq,
-                            const ProofLayout& P, const uint32_t* d_count = nullptr);
+                            const ProofLayout& P);
 // requests: OPEN_REQ_WORDS words each
 hipError_t launch_col_open(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const uint32_t* outer_nodes,
                            uint64_t outer_stride_nodes, int logChunks, const uint32_t* d_req, int nreq,
                            const ProofLayout& P, const uint32_t* tabs, const uint32_t* d_dlev,
-                           const DictPlan* d_plans, const uint32_t* d_dtabs, const DictCol* d_dcols,
-                           const uint32_t* d_count = nullptr);
+                           const DictPlan* d_plans, const uint32_t* d_dtabs, const DictCol* d_dcols);
 
 }  // namespace sezkp

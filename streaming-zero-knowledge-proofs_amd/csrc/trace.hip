@@ -1330,10 +1330,8 @@ __global__ void __launch_bounds__(TR_THREADS) k_col_open(TraceDev T, const ColTe
                                                          const uint32_t* __restrict__ dlev,
                                                          const DictPlan* __restrict__ plans,
                                                          const uint32_t* __restrict__ dtabs,
-                                                         const DictCol* __restrict__ dcols,
-                                                         const uint32_t* __restrict__ count) {
+                                                         const DictCol* __restrict__ dcols) {
   __shared__ uint32_t lds[8][1024];
-  if (count && blockIdx.x >= *count) return;  // grid sized for the most requests a rank can own
   const uint32_t* rq = req + OPEN_REQ_WORDS * (uint64_t)blockIdx.x;
   const int c = rq[0];
   const uint64_t row = (uint64_t)rq[1] | ((uint64_t)rq[2] << 32);
@@ -1790,7 +1788,7 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
                                                                    const uint32_t* __restrict__ tabs,
                                                                    uint32_t* __restrict__ outer, uint64_t outer_stride,
                                                                    uint64_t row0, uint64_t row_end,
-                                                                   uint32_t* __restrict__ dlev, int kmin, int kmax) {
+                                                                   uint32_t* __restrict__ dlev) {
   __shared__ uint32_t lds[2][8][DICT_WG_LANES];
   // (XCD-interleaved column orders, so that one XCD's workgroups gather
   // from one column's tables at a time, measured slower in rounds 1 and 3)
@@ -1799,7 +1797,6 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
   const ColTemplate* ctp = tmpl + dc.col;
   const ColTemplate ct = *ctp;
   const DictPlan P = plans[by];
-  if (P.K < kmin || P.K > kmax) return;  // the other launch's column (uniform per WG)
   const uint32_t* tab = tabs + 8 * dc.tab;
   const int lane = threadIdx.x;
   // high-K columns give each lane more rows (fewer LDS levels per row)
@@ -1908,14 +1905,13 @@ static hipError_t dict_shape_ok(const TraceDev& T, uint64_t row0, uint64_t nrows
   if (row0 + nrows > T.n || (nrows != T.n && (row0 % DICT_WG_ROWS || nrows % DICT_WG_ROWS))) return hipErrorInvalidValue;
   return hipSuccess;
 }
-// The dictionary commitment in three steps, in this order on one stream:
-// ranges + plans + reuse flags, table levels [lvl_lo, lvl_hi) of the columns
-// marked for rebuild, and the commit of the columns with kmin <= K <= kmax
-// (every level 0..K of a column must have been launched before its commit).
-static hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,
-                                      const DictCol* d_dcols, int ndict, int64_t* d_part, DictPlan* d_plans,
-                                      uint64_t row0, uint64_t nrows, uint32_t tab_cap, uint64_t plan_rows,
-                                      const DictCache& dc) {
+// The dictionary commitment, in this order on one stream: ranges + plans +
+// reuse flags, the table levels of the columns marked for rebuild (every
+// level 0..K of a column before its commit), and the commit of every column.
+hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
+                              int ndict, int64_t* d_part, DictPlan* d_plans, uint32_t* d_dtabs, uint32_t* outer_nodes,
+                              uint64_t outer_stride_nodes, uint64_t row0, uint64_t nrows, uint32_t* d_dlev,
+                              const DictCache& dc, uint32_t tab_cap, uint64_t plan_rows) {
   if (ndict == 0) return hipSuccess;
   hipError_t e = dict_shape_ok(T, row0, nrows);
   if (e != hipSuccess) return e;
@@ -1929,50 +1925,22 @@ static hipError_t launch_dict_prepare(hipStream_t st, const TraceDev& T, const C
   if ((e = hipGetLastError()) != hipSuccess) return e;
   hipLaunchKernelGGL(k_dict_plan, dim3(ndict), dim3(TR_THREADS), 0, st, d_part, nparts, T.n,
                      plan_rows ? plan_rows : nrows, d_dcols, d_plans, tab_cap, dc);
-  return hipGetLastError();
-}
-static hipError_t launch_dict_levels(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
-                                     const DictPlan* d_plans, const DictCache& dc, uint32_t* d_dtabs, int lvl_lo,
-                                     int lvl_hi) {
-  if (lvl_lo < 0 || lvl_hi > DICT_LEVELS) return hipErrorInvalidValue;
-  for (int l = lvl_lo; l < lvl_hi; l++) {
+  if ((e = hipGetLastError()) != hipSuccess) return e;
+  for (int l = 0; l < DICT_LEVELS; l++) {
     // one flat launch per level (and per DICT_FLAT_MAX columns): all WGs
     // share every column's entries
     for (int c0 = 0; c0 < ndict; c0 += DICT_FLAT_MAX) {
       const int nc = ndict - c0 < DICT_FLAT_MAX ? ndict - c0 : DICT_FLAT_MAX;
       hipLaunchKernelGGL(k_dict_level, dim3(DICT_FLAT_WGS), dim3(TR_THREADS), 0, st, d_tmpl, d_dcols + c0,
                          d_plans + c0, dc.reuse + c0, dc.lvl_seq, dc.seq, d_dtabs, nc, l);
-      hipError_t e = hipGetLastError();
-      if (e != hipSuccess) return e;
+      if ((e = hipGetLastError()) != hipSuccess) return e;
     }
   }
-  return hipSuccess;
-}
-static hipError_t launch_dict_commit_cols(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl,
-                                          const DictCol* d_dcols, int ndict, const DictPlan* d_plans,
-                                          const uint32_t* d_dtabs, uint32_t* outer_nodes, uint64_t outer_stride_nodes,
-                                          uint64_t row0, uint64_t nrows, uint32_t* d_dlev, int kmin, int kmax) {
-  if (ndict == 0) return hipSuccess;
-  hipError_t e = dict_shape_ok(T, row0, nrows);
-  if (e != hipSuccess) return e;
   const uint64_t wg_rows = (uint64_t)DICT_WG_LANES << DICT_LANE_LOG;  // rows of a WG at a = 0
   const unsigned gx = (unsigned)((nrows + wg_rows - 1) / wg_rows);
   hipLaunchKernelGGL(k_col_commit_dict, dim3(gx, ndict), dim3(DICT_WG_LANES), 0, st, T, d_tmpl, d_dcols, d_plans, d_dtabs,
-                     outer_nodes, outer_stride_nodes, row0, row0 + nrows, d_dlev, kmin, kmax);
+                     outer_nodes, outer_stride_nodes, row0, row0 + nrows, d_dlev);
   return hipGetLastError();
-}
-hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const DictCol* d_dcols,
-                              int ndict, int64_t* d_part, DictPlan* d_plans, uint32_t* d_dtabs, uint32_t* outer_nodes,
-                              uint64_t outer_stride_nodes, uint64_t row0, uint64_t nrows, uint32_t* d_dlev,
-                              const DictCache& dc, uint32_t tab_cap, uint64_t plan_rows) {
-  hipError_t e =
-      launch_dict_prepare(st, T, d_tmpl, d_dcols, ndict, d_part, d_plans, row0, nrows, tab_cap, plan_rows, dc);
-  if (e == hipSuccess && ndict)
-    e = launch_dict_levels(st, d_tmpl, d_dcols, ndict, d_plans, dc, d_dtabs, 0, DICT_LEVELS);
-  if (e == hipSuccess)
-    e = launch_dict_commit_cols(st, T, d_tmpl, d_dcols, ndict, d_plans, d_dtabs, outer_nodes, outer_stride_nodes, row0,
-                                nrows, d_dlev, -1, DICT_LEVELS);
-  return e;
 }
 
 hipError_t launch_col_commit(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const uint32_t* d_work,
@@ -2040,12 +2008,11 @@ hipError_t launch_air_audit(hipStream_t st, const TraceDev& T, const AirAuditOut
 hipError_t launch_col_open(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const uint32_t* outer_nodes,
                            uint64_t outer_stride_nodes, int logChunks, const uint32_t* d_req, int nreq,
                            const ProofLayout& P, const uint32_t* tabs, const uint32_t* d_dlev,
-                           const DictPlan* d_plans, const uint32_t* d_dtabs, const DictCol* d_dcols,
-                           const uint32_t* d_count) {
+                           const DictPlan* d_plans, const uint32_t* d_dtabs, const DictCol* d_dcols) {
   if (nreq == 0) return hipSuccess;
   if ((uint64_t)nreq > (uint64_t)P.nq * P.open_per_q) return hipErrorInvalidValue;
   hipLaunchKernelGGL(k_col_open, dim3(nreq), dim3(TR_THREADS), 0, st, T, d_tmpl, outer_nodes, outer_stride_nodes,
-                     logChunks, d_req, P, tabs, d_dlev, d_plans, d_dtabs, d_dcols, d_count);
+                     logChunks, d_req, P, tabs, d_dlev, d_plans, d_dtabs, d_dcols);
   return hipGetLastError();
 }
 

@@ -1,0 +1,182 @@
+// prove_plan_check.cpp — the upload's planning arithmetic (prove_plan.h) as a
+// stand-alone host program (no GPU, no ROCm headers, no Python): prints the
+// plan of one trace shape as JSON, for tests/test_prove_plan_host.py.
+//
+//   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -o prove_plan_check tools/prove_plan_check.cpp
+//   ./prove_plan_check TAU RANK WORLD SHARDED USE_DICT WHAT STEP_START...
+//
+// WHAT: a comma list of shape, columns, fri, proof. STEP_START: the nblk + 1
+// block boundaries, or the one word logn:L for the shape of 2^L rows without
+// block boundaries (shape, fri and proof only; the shard's chunks and blocks
+// are not planned). A shape the planner rejects prints {"error": "..."} and
+// exits 2.
+#include <stdio.h>
+#include <stdlib.h>
+#include <string.h>
+
+#include <string>
+#include <vector>
+
+#include "../streaming-zero-knowledge-proofs_amd/csrc/prove_plan.h"
+
+using namespace sezkp;
+
+template <class V>
+static void put_list(const char* name, const V& v) {
+  printf("\"%s\": [", name);
+  for (size_t i = 0; i < v.size(); i++) printf("%s%llu", i ? "," : "", (unsigned long long)v[i]);
+  printf("]");
+}
+static void put_ranges(const char* name, const std::vector<JobRange>& v) {
+  printf("\"%s\": [", name);
+  for (size_t i = 0; i < v.size(); i++) printf("%s[%zu,%d]", i ? "," : "", v[i].first, v[i].second);
+  printf("]");
+}
+
+int main(int argc, char** argv) {
+  if (argc < 8) {
+    fprintf(stderr, "usage: %s TAU RANK WORLD SHARDED USE_DICT WHAT STEP_START...\n", argv[0]);
+    return 1;
+  }
+  const uint32_t tau = (uint32_t)strtoul(argv[1], nullptr, 10);
+  const int rank = atoi(argv[2]), world = atoi(argv[3]);
+  const bool sharded = atoi(argv[4]) != 0, use_dict = atoi(argv[5]) != 0;
+  const std::string what = std::string(",") + argv[6] + ",";
+  auto want = [&](const char* w) { return what.find(std::string(",") + w + ",") != std::string::npos; };
+  if (world < 1 || world > 8 || (world & (world - 1)) || rank < 0 || rank >= world) {
+    fprintf(stderr, "world must be a power of two <= 8 and 0 <= rank < world\n");
+    return 1;
+  }
+  const int logP = ilog2((uint64_t)world);
+  std::vector<uint64_t> ss;
+  int only_logn = -1;
+  if (strncmp(argv[7], "logn:", 5) == 0) only_logn = atoi(argv[7] + 5);
+  else
+    for (int i = 7; i < argc; i++) ss.push_back(strtoull(argv[i], nullptr, 10));
+  try {
+    ShapePlan s;
+    if (only_logn >= 0) s = shape_of_logn(tau, 1, only_logn, rank, logP, sharded);
+    else s = plan_shape(tau, ss.data(), (uint32_t)(ss.size() - 1), rank, logP, sharded);
+    printf("{");
+    const char* sep = "";
+    if (want("shape")) {
+      printf("\"shape\": {\"n\": %llu, \"N\": %llu, \"logn\": %d, \"logN\": %d, \"ncols\": %d, \"logChunks\": %d, "
+             "\"M\": %llu, \"logM\": %d, \"rR\": %d, \"tree_wg_log\": %d, \"full_lde\": %d, \"ch_lo\": %llu, "
+             "\"ch_hi\": %llu, \"blk_lo\": %u, \"blk_cnt\": %u, \"tree_stop\": %d, \"wg_stop\": %d}",
+             (unsigned long long)s.n, (unsigned long long)s.N, s.logn, s.logN, s.ncols, s.logChunks,
+             (unsigned long long)s.M, s.logM, s.rR, s.tree_wg_log, (int)s.full_lde, (unsigned long long)s.ch_lo,
+             (unsigned long long)s.ch_hi, s.blk_lo, s.blk_cnt, s.tree_stop(), s.wg_stop());
+      sep = ", ";
+    }
+    std::vector<std::string> labels;
+    if (only_logn >= 0)
+      for (int c = 0; c < s.ncols; c++) labels.push_back(label_of(c, tau));
+    if (only_logn < 0 && (want("columns") || want("proof"))) {
+      const ColumnPlan c = plan_columns(s, ss.data(), use_dict);
+      labels = c.labels;
+      if (want("columns")) {
+        printf("%s\"columns\": {\"tab_nodes\": %llu, \"tab_units\": %llu, ", sep, (unsigned long long)c.tab_nodes,
+               (unsigned long long)c.tab_units);
+        printf("\"cols\": [");
+        for (size_t i = 0; i < c.tmpl.size(); i++) {
+          const ColTemplate& t = c.tmpl[i];
+          printf("%s{\"label\": \"%s\", \"kind\": %u, \"tape\": %u, \"off\": %u, \"block_len\": %u, \"tab\": %lld, "
+                 "\"tab_log\": %u}",
+                 i ? "," : "", c.labels[i].c_str(), t.kind, t.tape, t.off, t.block_len,
+                 t.tab == NO_TAB ? -1ll : (long long)t.tab, t.tab_log);
+        }
+        printf("], \"dcols\": [");
+        for (size_t i = 0; i < c.dcols.size(); i++)
+          printf("%s{\"col\": %u, \"mv\": %lld, \"tab\": %llu}", i ? "," : "", c.dcols[i].col,
+                 c.dcols[i].mv == NO_DICT ? -1ll : (long long)c.dcols[i].mv, (unsigned long long)c.dcols[i].tab);
+        printf("], \"dict_of\": [");
+        for (size_t i = 0; i < c.dict_of.size(); i++)
+          printf("%s%lld", i ? "," : "", c.dict_of[i] == NO_DICT ? -1ll : (long long)c.dict_of[i]);
+        printf("], ");
+        put_list("tab_cols", c.tab_cols);
+        printf(", ");
+        put_list("pw_cols", c.pw_cols);
+        printf(", ");
+        put_list("pw_chunks", c.pw_chunks);
+        printf(", ");
+        put_list("dense_chunk", c.dense_chunk);
+        printf(", ");
+        put_list("work", c.work);
+        printf("}");
+        sep = ", ";
+      }
+    }
+    if (want("fri")) {
+      const FriPlan f = plan_fri(s);
+      printf("%s\"fri\": {\"k\": %d, \"lde_vals\": %llu, \"run_vals\": %llu, \"rep_vals\": %llu, \"total_nodes\": %llu, "
+             "\"root_slots\": %d, \"tail_first\": %d, \"forest_wgs\": %u, \"tailbuf\": %d, \"njobs\": %zu, ",
+             sep, f.k, (unsigned long long)f.lde_vals, (unsigned long long)f.run_vals, (unsigned long long)f.rep_vals,
+             (unsigned long long)f.total_nodes, f.root_slots, f.tail_first, f.forest_wgs, (int)f.tailbuf,
+             f.jobs.size());
+      put_list("rep16", f.rep16);
+      printf(", \"layers\": [");
+      for (size_t r = 0; r < f.layers.size(); r++) {
+        const FriLayerPlan& L = f.layers[r];
+        printf("%s{\"run\": %d, \"buf\": %d, \"val_off\": %llu, \"val_len\": %llu, \"node_off\": %llu, \"logLen\": %d, "
+               "\"lstore\": %d, \"root_slot\": %d, \"has_cap\": %d, \"cap_off\": %llu, \"cap_logLen\": %d, "
+               "\"cap_lstore\": %d, \"cap_root_slot\": %d, \"gather_off\": %llu, \"gather_nodes\": %llu}",
+               r ? "," : "", (int)L.run, L.buf, (unsigned long long)L.val_off, (unsigned long long)L.val_len,
+               (unsigned long long)L.node_off, L.logLen, L.lstore, L.root_slot, (int)L.has_cap,
+               (unsigned long long)L.cap_off, L.cap_logLen, L.cap_lstore, L.cap_root_slot,
+               (unsigned long long)L.gather_off, (unsigned long long)L.gather_nodes);
+      }
+      printf("], \"forest\": [");
+      for (size_t i = 0; i < f.forest.size(); i++)
+        printf("%s{\"layer\": %d, \"wg_start\": %u, \"stop\": %u, \"wgs\": %llu}", i ? "," : "", f.forest[i].layer,
+               f.forest[i].wg_start, f.forest[i].stop,
+               (unsigned long long)(1ULL << (f.layers[f.forest[i].layer].logLen - s.tree_wg_log)));
+      printf("], ");
+      put_ranges("jobs0", f.jobs0);
+      printf(", ");
+      put_ranges("jobsF", f.jobsF);
+      printf(", ");
+      put_ranges("jobsL0", f.jobsL0);
+      printf(", ");
+      put_ranges("jobsLR", f.jobsLR);
+      // per pass: the layer, whether the cap, from / to, and whether it reads gathered roots (its first job's)
+      printf(", \"passes\": [");
+      bool first = true;
+      for (const std::vector<JobRange>* v : {&f.jobs0, &f.jobsF, &f.jobsL0, &f.jobsLR})
+        for (const JobRange& p : *v) {
+          // a pass of jobsF / jobsLR holds jobs of several layers: list each run of one layer
+          for (size_t i = p.first; i < p.first + (size_t)p.second;) {
+            size_t j = i;
+            while (j < p.first + (size_t)p.second && f.job_layer[j] == f.job_layer[i]) j++;
+            printf("%s{\"first\": %zu, \"count\": %zu, \"layer\": %d, \"cap\": %d, \"from\": %d, \"to\": %d, "
+                   "\"gath\": %d, \"logLen\": %d}",
+                   first ? "" : ",", i, j - i, f.job_layer[i], (int)f.job_cap[i], f.jobs[i].from, f.jobs[i].to,
+                   (int)(f.jobs[i].gath != nullptr), f.jobs[i].tree.logLen);
+            first = false;
+            i = j;
+          }
+        }
+      printf("]}");
+      sep = ", ";
+    }
+    if (want("proof")) {
+      const ProofPlan p = plan_proof(s, labels);
+      const ProofLayout& PL = p.PL;
+      printf("%s\"proof\": {\"hdr_bytes\": %zu, \"open_bytes\": %llu, \"q_bytes\": %llu, \"fr_off\": %llu, "
+             "\"fq_off\": %llu, \"fq_bytes\": %llu, \"tail_off\": %llu, \"total\": %llu, \"open_per_q\": %u, "
+             "\"nq\": %u, \"k\": %d, \"tau\": %u, \"max_fri_req\": %zu, \"max_open_req\": %zu, ",
+             sep, p.hdr_bytes, (unsigned long long)PL.open_bytes, (unsigned long long)PL.q_bytes,
+             (unsigned long long)PL.fr_off, (unsigned long long)PL.fq_off, (unsigned long long)PL.fq_bytes,
+             (unsigned long long)PL.tail_off, (unsigned long long)PL.total, PL.open_per_q, PL.nq, PL.k, PL.tau,
+             p.max_fri_req, p.max_open_req);
+      put_list("root_pos", p.root_pos);
+      printf(", \"header_hex\": \"");
+      for (uint8_t b : p.header) printf("%02x", b);
+      printf("\"}");
+    }
+    printf("}\n");
+  } catch (const PlanError& e) {
+    printf("{\"error\": \"%s\"}\n", e.msg.c_str());
+    return 2;
+  }
+  return 0;
+}
