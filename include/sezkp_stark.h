@@ -82,7 +82,22 @@ int32_t sezkp_stark_v1_prove(const sezkp_block_view* blocks, const uint8_t manif
 /* Same, returning the whole ProofArtifact as CBOR (io.rs:176-183). */
 int32_t sezkp_stark_v1_prove_artifact_cbor(const sezkp_block_view* blocks, const uint8_t manifest_root[32],
                                            uint32_t flags, sezkp_buf* artifact_cbor, char* err, size_t err_len);
-/* StarkV1::verify (lib.rs:144-162 -> v1/verify.rs:60-196) on the host CPU. */
+/* StarkV1::verify (lib.rs:144-162 -> v1/verify.rs:60-196) on the host CPU.
+ * Verdict and message are the reference's for the same proof, except where
+ * this verifier is stricter on purpose (tests/proof_corpus.py):
+ *   - bytes after the proof: SEZKP_E_VERIFY "trailing bytes in proof". The
+ *     reference accepts them (bincode 1.3's top-level deserialize ignores
+ *     trailing bytes); a verifier library should not accept two encodings of
+ *     one proof.
+ *   - a FRI layer count other than log2(domain_n) + 1: SEZKP_E_VERIFY "FRI
+ *     layer count does not match domain_n" before FRI starts; the reference
+ *     goes on with the count the proof gives.
+ *   - manifest_root, when not NULL, is compared with the proof's own copy
+ *     first ("manifest root mismatch"); the reference compares it with the
+ *     artifact envelope's, which this call does not see.
+ *   - a proof that does not decode is SEZKP_E_DECODE with this library's
+ *     wording ("truncated proof bytes", "bad length prefix", "column label is
+ *     not valid UTF-8"), not bincode's. */
 int32_t sezkp_stark_v1_verify(const uint8_t* proof_bytes, size_t len, const sezkp_block_view* blocks,
                               const uint8_t manifest_root[32], char* err, size_t err_len);
 

@@ -93,6 +93,27 @@ def blake3(data: bytes, out_len: int = 32) -> bytes:
     return out[:out_len]
 
 
+# The hash the helpers below call. prove_v1 / verify_v1 take an optional
+# `blake3=` (same signature as blake3 above: data, out_len=32) for bulk work,
+# e.g. the C oracle's; it is in force for the duration of that one call.
+_b3 = blake3
+
+
+class _hashing:
+    def __init__(self, fn):
+        self.fn = fn
+
+    def __enter__(self):
+        global _b3
+        self.prev = _b3
+        if self.fn is not None:
+            _b3 = self.fn
+
+    def __exit__(self, *exc):
+        global _b3
+        _b3 = self.prev
+
+
 # ---------------------------------------------------------------- Transcript
 class Transcript:
     """crates/sezkp-crypto/src/lib.rs:74-123 — the BLAKE3 state is the hash of
@@ -111,7 +132,7 @@ class Transcript:
 
     def challenge(self, label: str, n: int) -> bytes:
         lb = label.encode()
-        out = blake3(self.stream + b"challenge" + struct.pack("<I", len(lb)) + lb, n)
+        out = _b3(self.stream + b"challenge" + struct.pack("<I", len(lb)) + lb, n)
         self.stream += b"after_challenge" + struct.pack("<I", len(lb)) + lb
         return out
 
@@ -142,16 +163,16 @@ def idft(y, omega):  # lib.rs:209-224
 
 # -------------------------------------------------------------------- Merkle
 def h2(a, b):
-    return blake3(a + b)
+    return _b3(a + b)
 
 
 def leaf(v):
-    return blake3(struct.pack("<Q", v))
+    return _b3(struct.pack("<Q", v))
 
 
 def leaf_lab(v, label):
     lb = label.encode()
-    return blake3(b"col_leaf" + struct.pack("<I", len(lb)) + lb + struct.pack("<Q", v))
+    return _b3(b"col_leaf" + struct.pack("<I", len(lb)) + lb + struct.pack("<Q", v))
 
 
 def tree_levels(leaves):  # merkle.rs:46-71
@@ -250,8 +271,38 @@ def compose(rows, tau, i, a):  # air.rs:49-136 with alpha reuse (prover.rs:86-98
     return acc % P
 
 
-def prove_v1(blocks, manifest_root: bytes) -> bytes:
+FORGE_HOOKS = ("rows", "enc", "layer", "next_row", "query_rows", "fri_roots")
+
+
+def prove_v1(blocks, manifest_root: bytes, forge=None, blake3=None) -> bytes:
+    """The reference prover; with forge=None its bytes. `forge` is a dict of
+    optional hooks that make a proof the reference prover never would, every
+    Merkle path in it still valid, so that only the verifier's algebraic or
+    structural check can catch it:
+      rows(rows, tau) -> rows      edits the row snapshots (values mod p)
+      enc(label, value) -> int     the 8 bytes written for a column value, in
+                                   its leaf and its opening alike (v + p is
+                                   legal for v < 2^32 - 1); the composition
+                                   keeps the canonical value
+      layer(r, values) -> values   edits FRI layer r >= 1 before it is
+                                   committed; later layers fold from it;
+                                   r = k is the final value
+      next_row(row) -> row'        the row opened as next_mv / next_head
+      query_rows(rows) -> rows     the rows opened, after they were drawn
+      fri_roots(roots) -> roots    the roots written; the row queries are then
+                                   drawn as the verifier will draw them from
+                                   what this returns (verify.rs:119-131)
+    `blake3`: an optional hash (data, out_len=32) used instead of the module's."""
+    with _hashing(blake3):
+        return _prove_v1(blocks, manifest_root, dict(forge or {}))
+
+
+def _prove_v1(blocks, manifest_root, forge):
+    assert set(forge) <= set(FORGE_HOOKS), sorted(set(forge) - set(FORGE_HOOKS))
     rows, tau = row_snapshots(blocks)
+    if "rows" in forge:
+        rows = [{k: v % P for k, v in r.items()} for r in forge["rows"]([dict(r) for r in rows], tau)]
+    enc = forge.get("enc", lambda _label, v: v)
     n = len(rows)
     assert n and n & (n - 1) == 0
     labs = labels(tau)
@@ -262,7 +313,7 @@ def prove_v1(blocks, manifest_root: bytes) -> bytes:
     # column commitments with 1024-row chunks (openings.rs:306-398)
     chunk_trees, outer_trees = {}, {}
     for lab in labs:
-        lv = [leaf_lab(r[lab], lab) for r in rows]
+        lv = [leaf_lab(enc(lab, r[lab]), lab) for r in rows]
         cts = [tree_levels(lv[s:s + 1024]) for s in range(0, n, 1024)]
         chunk_trees[lab] = cts
         outer_trees[lab] = tree_levels([t[-1][0] for t in cts])
@@ -295,6 +346,8 @@ def prove_v1(blocks, manifest_root: bytes) -> bytes:
     layers = [lde]
     trees = [tree_levels([leaf(v) for v in lde])]
     roots = [trees[0][-1][0]]
+    tr_ood = Transcript.__new__(Transcript)  # the state the verifier's tr_rows starts from
+    tr_ood.stream = tr.stream
     tr.absorb("fri_layer_root", roots[0])
     bb = tr.challenge("fri_betas", 8 * k)
     betas = [int.from_bytes(bb[8 * i:8 * i + 8], "little") % P for i in range(k)]
@@ -302,14 +355,28 @@ def prove_v1(blocks, manifest_root: bytes) -> bytes:
         cur = layers[-1]
         h = len(cur) // 2
         nxt = [(cur[i] + betas[r] * cur[i + h]) % P for i in range(h)]
+        if "layer" in forge:
+            nxt = [v % P for v in forge["layer"](r + 1, list(nxt))]
+            assert len(nxt) == h
         layers.append(nxt)
         trees.append(tree_levels([leaf(v) for v in nxt]))
         roots.append(trees[-1][-1][0])
         tr.absorb("fri_layer_root", roots[-1])
+    out_roots = roots
+    if "fri_roots" in forge:
+        out_roots = list(forge["fri_roots"](list(roots)))
+        tr = tr_ood
+        if out_roots:
+            tr.absorb("fri_layer_root", out_roots[0])
+            tr.challenge("fri_betas", 8 * (len(out_roots) - 1))
+            for rt in out_roots[1:]:
+                tr.absorb("fri_layer_root", rt)
     qb = tr.challenge("row_queries", 240)
     qrows = [int.from_bytes(qb[8 * i:8 * i + 8], "little") % n for i in range(30)]
     fb = tr.challenge("row_queries", 240)
     frows = [int.from_bytes(fb[8 * i:8 * i + 8], "little") % N for i in range(30)]
+    if "query_rows" in forge:
+        qrows = list(forge["query_rows"](list(qrows)))
 
     U = lambda x: struct.pack("<Q", x)
     vec32 = lambda xs: U(len(xs)) + b"".join(xs)
@@ -317,22 +384,24 @@ def prove_v1(blocks, manifest_root: bytes) -> bytes:
     def opening(lab, row):
         ch, ii = row // 1024, row % 1024
         t = chunk_trees[lab][ch]
-        return (U(rows[row][lab]) + U(row) + U(ch) + U(ii) + t[-1][0] + vec32(tree_open(t, ii))
+        return (U(enc(lab, rows[row][lab])) + U(row) + U(ch) + U(ii) + t[-1][0] + vec32(tree_open(t, ii))
                 + vec32(tree_open(outer_trees[lab], ch)))
 
     out = U(N) + U(tau) + U(len(labs))
     for lab in labs:
         out += U(len(lab)) + lab.encode() + outer_trees[lab][-1][0]
-    out += U(30)
+    out += U(len(qrows))
     for row in qrows:
         ip1 = row + 1 if row + 1 < n else 0
+        if "next_row" in forge:
+            ip1 = forge["next_row"](row)
         out += U(row) + U(tau)
         for r in range(tau):
             out += (opening(f"mv_{r}", row) + opening(f"mv_{r}", ip1) + opening(f"wflag_{r}", row)
                     + opening(f"wsym_{r}", row) + opening(f"head_{r}", row) + opening(f"head_{r}", ip1)
                     + opening(f"winlen_{r}", row) + opening(f"in_off_{r}", row) + opening(f"out_off_{r}", row))
         out += opening("is_first", row) + opening("is_last", row) + opening("input_mv", row)
-    out += vec32(roots) + U(30)
+    out += vec32(out_roots) + U(30)
     for idx0 in frows:
         pos = [idx0]
         ln = N
@@ -365,10 +434,14 @@ class _Rd:
         return s
 
     def u64(self):
-        return struct.unpack("<Q", self.take(8))[0]
+        if self.p + 8 > len(self.b):
+            raise ValueError("truncated proof bytes")
+        self.p += 8
+        return struct.unpack_from("<Q", self.b, self.p - 8)[0]
 
     def vec32(self):
-        return [self.take(32) for _ in range(self.u64())]
+        raw = self.take(32 * self.u64())  # a count the bytes cannot hold is a short read either way
+        return [raw[i:i + 32] for i in range(0, len(raw), 32)]
 
 
 def _opening(rd):  # proof.rs:44-66
@@ -377,7 +450,15 @@ def _opening(rd):  # proof.rs:44-66
 
 
 def parse_proof_v1(b: bytes) -> dict:
+    """The ProofV1 at the start of b. "trailing": the bytes left after it, which
+    bincode 1.3's top-level `deserialize` (lib.rs:159) ignores."""
     rd = _Rd(b)
+    pf = _parse_v1(rd)
+    pf["trailing"] = len(rd.b) - rd.p
+    return pf
+
+
+def _parse_v1(rd) -> dict:
     pf = {"domain_n": rd.u64(), "tau": rd.u64(), "col_roots": []}
     for _ in range(rd.u64()):
         lab = rd.take(rd.u64()).decode()
@@ -412,19 +493,30 @@ def merkle_verify(root, leaf_h, idx, sibs):  # merkle.rs:111-126 (MerkleTree::ve
 
 def _leaf_lab_raw(value_le: bytes, label: str):  # merkle.rs:132-147 over the opened bytes as given
     lb = label.encode()
-    return blake3(b"col_leaf" + struct.pack("<I", len(lb)) + lb + bytes(value_le))
+    return _b3(b"col_leaf" + struct.pack("<I", len(lb)) + lb + bytes(value_le))
 
 
-def verify_v1(proof_bytes: bytes, tau_blocks=None):
+DECODE_ERROR = "proof decode error: "  # what every verdict of a failed bincode read starts with
+
+
+def verify_v1(proof_bytes: bytes, tau_blocks=None, blake3=None):
     """verify_v1 (crates/sezkp-stark/src/v1/verify.rs:60-196) with fri_verify
     (fri.rs:130-222) and verify_chunked_open (merkle.rs:243-280). Returns None
     when the proof is accepted, else the reference's error text. `tau_blocks`:
-    the block windows' tau (verify.rs:73-81), or None for no blocks."""
+    the block windows' tau (verify.rs:73-81), or None for no blocks. `blake3`:
+    an optional hash (data, out_len=32) used instead of the module's. Bytes
+    after the proof are ignored, as bincode 1.3's top-level `deserialize`
+    ignores them (lib.rs:159)."""
+    with _hashing(blake3):
+        return _verify_v1(proof_bytes, tau_blocks)
+
+
+def _verify_v1(proof_bytes, tau_blocks):
     fe = lambda le: int.from_bytes(le, "little") % P
     try:
         pf = parse_proof_v1(proof_bytes)
-    except ValueError as e:
-        return str(e)
+    except ValueError as e:  # a short read, or a label that is not UTF-8 (a Rust String): bincode's Err
+        return DECODE_ERROR + str(e)
     if pf["domain_n"] % 8:
         return "FRI domain_n not multiple of blowup"
     n = pf["domain_n"] // 8
@@ -503,7 +595,7 @@ def verify_v1(proof_bytes: bytes, tau_blocks=None):
     bb = tr.challenge("fri_betas", 8 * (nl - 1))
     betas = [int.from_bytes(bb[8 * i:8 * i + 8], "little") % P for i in range(nl - 1)]
     final = pf["fri_final_value_le"]
-    if roots[nl - 1] != blake3(bytes(final)):
+    if roots[nl - 1] != _b3(bytes(final)):
         return "final FRI value mismatch with last root"
     for fq in pf["fri_queries"]:
         pos, pairs = fq["positions"], fq["pairs"]
@@ -516,7 +608,7 @@ def verify_v1(proof_bytes: bytes, tau_blocks=None):
             half = ln // 2
             j = idx ^ half
             vi_le, pi, vj_le, pj = pairs[l]
-            if not (merkle_verify(roots[l], blake3(vi_le), idx, pi) and merkle_verify(roots[l], blake3(vj_le), j, pj)):
+            if not (merkle_verify(roots[l], _b3(vi_le), idx, pi) and merkle_verify(roots[l], _b3(vj_le), j, pj)):
                 return f"FRI Merkle path failed at layer {l}"
             vi, vj = fe(vi_le), fe(vj_le)
             lower, upper = (vi, vj) if idx < half else (vj, vi)

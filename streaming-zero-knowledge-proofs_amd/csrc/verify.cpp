@@ -138,6 +138,36 @@ void leaf_labeled(const uint8_t v[8], const std::string& label, uint8_t out[32])
 }
 uint64_t fe(const uint8_t v[8]) { return rd64(v) % GL_P_HOST; }
 
+// A column label is a Rust String (proof.rs:18): bincode refuses bytes that
+// are not UTF-8 as str::from_utf8 does (no overlong forms, no surrogates,
+// nothing past U+10FFFF), and the proof with them.
+bool is_utf8(const uint8_t* s, uint64_t n) {
+  uint64_t i = 0;
+  while (i < n) {
+    const uint8_t c = s[i];
+    uint64_t more;
+    uint8_t lo = 0x80, hi = 0xBF;  // the range of the first continuation byte
+    if (c < 0x80) more = 0;
+    else if (c >= 0xC2 && c <= 0xDF) more = 1;
+    else if (c >= 0xE0 && c <= 0xEF) {
+      more = 2;
+      if (c == 0xE0) lo = 0xA0;
+      if (c == 0xED) hi = 0x9F;
+    } else if (c >= 0xF0 && c <= 0xF4) {
+      more = 3;
+      if (c == 0xF0) lo = 0x90;
+      if (c == 0xF4) hi = 0x8F;
+    } else return false;
+    if (n - i - 1 < more) return false;
+    for (uint64_t k = 1; k <= more; k++) {
+      const uint8_t d = s[i + k];
+      if (d < (k == 1 ? lo : 0x80) || d > (k == 1 ? hi : 0xBF)) return false;
+    }
+    i += 1 + more;
+  }
+  return true;
+}
+
 // ------------------------------------------------------------------ parse
 // The walk of the bincode ProofV1 (proof.rs:80-98) in the order and with the
 // bounds checks of the reference's deserialiser, then the jobs. Every length
@@ -174,6 +204,7 @@ void parse_v1(VerifyItem& it, ParsedProof& P) {
   for (uint64_t c = 0; c < P.ncols; c++) {
     const uint64_t l = r.count(1);
     const uint64_t lo = r.raw(l);
+    if (!is_utf8(b + lo, l)) throw VErr{SEZKP_E_DECODE, "column label is not valid UTF-8"};
     it.col_roots.push_back(r.raw(32));
     col_of[std::string((const char*)b + lo, l)] = c;
   }

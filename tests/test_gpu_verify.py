@@ -9,13 +9,13 @@ path_to sibling cases use the 4096-row tau = 8 proof, whose openings carry two
 siblings there.
 
 `python tests/test_gpu_verify.py --dump-corpus DIR` (no GPU) writes the
-tampered, re-serialised, truncated and bit-flipped proofs of this module to
-DIR, one file each, for tools/verify_hostile.cpp.
+tampered, re-serialised, truncated and bit-flipped proofs of this module and
+the differential corpus of tests/proof_corpus.py to DIR, one file each, for
+tools/verify_hostile.cpp.
 """
 import ctypes as C
 import os
 import random
-import struct
 import subprocess
 import sys
 import threading
@@ -26,6 +26,7 @@ import pytest
 if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from conftest import GOLDEN, PKG  # noqa: E402
+from proof_corpus import _layout, _write_proof  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
@@ -104,57 +105,6 @@ def _agree(product, ctx, items):
 
 
 # ------------------------------------------------------------------ layout
-def _layout(b):
-    """Byte offsets of a bincode ProofV1 (proof.rs:80-98), the arithmetic of
-    test_verifier.py made a walk: openings as dicts of field offsets."""
-    u64 = lambda o: struct.unpack_from("<Q", b, o)[0]
-    L = {"cols": [], "rows": [], "fq": []}
-    p = 16
-    ncols = u64(p); L["ncols_at"] = p; p += 8
-    for _ in range(ncols):
-        ll = u64(p)
-        L["cols"].append({"len_at": p, "label": p + 8, "root": p + 8 + ll})
-        p += 8 + ll + 32
-    L["hdr"] = p
-
-    def opening(p):
-        a = u64(p + 64)
-        bq = u64(p + 72 + 32 * a)
-        o = {"value": p, "index": p + 8, "chunk_index": p + 16, "index_in_chunk": p + 24, "chunk_root": p + 32,
-             "n_in_at": p + 64, "path_in": p + 72, "n_in": a, "n_to_at": p + 72 + 32 * a,
-             "path_to": p + 80 + 32 * a, "n_to": bq}
-        return o, p + 80 + 32 * (a + bq)
-    L["nq_at"] = p
-    nq = u64(p); p += 8
-    for _ in range(nq):
-        row = {"row": p, "nt_at": p + 8, "opens": []}
-        nt = u64(p + 8); p += 16
-        for _ in range(9 * nt + 3):
-            o, p = opening(p)
-            row["opens"].append(o)
-        L["rows"].append(row)
-    L["nroots_at"] = p
-    nr = u64(p); p += 8
-    L["roots"] = p; p += 32 * nr
-    L["nroots"] = nr
-    nfq = u64(p); p += 8
-    for _ in range(nfq):
-        q = {"npos_at": p, "pos": p + 8, "pairs": []}
-        npos = u64(p); p += 8 + 8 * npos
-        npairs = u64(p); p += 8
-        for _ in range(npairs):
-            a = u64(p + 8)
-            c = u64(p + 16 + 32 * a + 8)
-            q["pairs"].append({"vi": p, "path_i": p + 16, "n_i": a, "vj": p + 16 + 32 * a,
-                               "path_j": p + 32 + 32 * a, "n_j": c})
-            p += 32 + 32 * (a + c)
-        L["fq"].append(q)
-    L["final"] = p
-    L["mroot"] = p + 8
-    assert p + 40 == len(b)
-    return L
-
-
 def _flip(proof, at, bit=0):
     b = bytearray(proof)
     b[at] ^= 1 << bit
@@ -201,36 +151,6 @@ def _designed(proofs):
     out.append(("length prefix", _flip(p128, first["n_in_at"] + 6), None, "bad length prefix"))
     out.append(("query count", _flip(p128, L["nq_at"]), None, "bad length prefix"))  # a 31st row is read from the FRI roots
     return out
-
-
-# ------------------------------------------------------------- bincode writer
-def _write_proof(pf):
-    """bincode 1.3 fixint LE writer over sezkp_oracle_py.parse_proof_v1's output."""
-    u64 = lambda x: struct.pack("<Q", x)
-    vec32 = lambda v: u64(len(v)) + b"".join(v)
-
-    def opening(o):
-        return (o["value_le"] + u64(o["index"]) + u64(o["chunk_index"]) + u64(o["index_in_chunk"]) + o["chunk_root"] +
-                vec32(o["path_in_chunk"]) + vec32(o["path_to_chunk"]))
-    out = [u64(pf["domain_n"]), u64(pf["tau"]), u64(len(pf["col_roots"]))]
-    for lab, r in pf["col_roots"]:
-        lb = lab.encode()
-        out += [u64(len(lb)), lb, r]
-    out.append(u64(len(pf["queries"])))
-    for q in pf["queries"]:
-        out += [u64(q["row"]), u64(len(q["per_tape"]))]
-        for t in q["per_tape"]:
-            out += [opening(t[k]) for k in ("mv", "next_mv", "write_flag", "write_sym", "head", "next_head", "win_len",
-                                            "in_off", "out_off")]
-        out += [opening(q[k]) for k in ("is_first", "is_last", "input_mv")]
-    out.append(vec32(pf["fri_roots"]))
-    out.append(u64(len(pf["fri_queries"])))
-    for f in pf["fri_queries"]:
-        out += [u64(len(f["positions"]))] + [u64(x) for x in f["positions"]] + [u64(len(f["pairs"]))]
-        for vi, pi, vj, pj in f["pairs"]:
-            out += [vi, vec32(pi), vj, vec32(pj)]
-    out += [pf["fri_final_value_le"], pf["manifest_root"]]
-    return b"".join(out)
 
 
 def _reserialised(proofs):
@@ -461,6 +381,8 @@ def _dump_corpus(out_dir):
     files += [(f"designed_{i:02d}", p) for i, (_, p, _, _) in enumerate(_designed(proofs))]
     files += [(f"reserialised_{i:02d}", p) for i, (_, p, _) in enumerate(_reserialised(proofs))]
     files += [(f"flip_{i:03d}", p) for i, p in enumerate(_random_flips(proofs["still_128"][2]))]
+    import proof_corpus  # the differential corpus (test_verifier_differential.py), family and number in the name
+    files += [(f"diff_{c.family}_{i:03d}", c.proof) for i, c in enumerate(proof_corpus.corpus(oracle_ctypes))]
     for name, p in files:
         with open(os.path.join(out_dir, name + ".bin"), "wb") as f:
             f.write(p)
