@@ -108,6 +108,15 @@ __device__ inline uint64_t gl_inv(uint64_t a) {
   uint64_t hi = gl_pow2k(gl_sqr(t31), 32);        // a^((2^32-2) * 2^32)
   return gl_mul(hi, t32);
 }
+__device__ __forceinline__ uint64_t gl_pow_dev(uint64_t b, uint64_t e) {
+  uint64_t r = 1;
+  while (e) {
+    if (e & 1) r = gl_mul(r, b);
+    b = gl_sqr(b);
+    e >>= 1;
+  }
+  return r;
+}
 
 // ------------------------------------------------------------------ BLAKE3
 #define B3_IV0 0x6A09E667u

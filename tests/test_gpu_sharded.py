@@ -201,11 +201,14 @@ def test_sharded_rejects_small_trace(gpu_ok, product):
     assert not L.lib.sezkp_ctx_create_sharded_host(0, 0, 3, C.byref(hc), err, 1024)  # world not a power of two
 
 
-@pytest.mark.parametrize("T,b,tau", [(1 << 12, 512, 2), (1 << 15, 200, 8)])
+# 2^12 rows: the smallest forced-sharded one-rank shape, whose layer 3 has the one-node cap
+# (plan_upper_jobs' `gath && from == top` job; tests/test_prove_plan_host.py finds the shape on the CPU)
+@pytest.mark.parametrize("T,b,tau", [(1 << 12, 512, 2), (1 << 15, 200, 8), (1 << 12, 256, 1)])
 def test_sharded_algorithm_over_rccl_one_rank(gpu_ok, product, oracle, monkeypatch, T, b, tau):
     """SEZKP_FORCE_SHARDED runs the sharded algorithm with a one-rank RCCL
     communicator: every RCCL call (allgather, all-to-all, allreduce) and the
-    run/cap layouts execute on the device, bit-exact with the oracle."""
+    run/cap layouts execute on the device, bit-exact with the oracle. With one
+    rank the last run layer's cap is a single node (the one-node-cap job)."""
     monkeypatch.setenv("SEZKP_FORCE_SHARDED", "1")
     blocks = product.synthetic_blocks(T, b, tau, 11)
     root = blocks.manifest_root()

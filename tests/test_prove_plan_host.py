@@ -271,3 +271,26 @@ def test_column_plan(plan, case, use_dict):
                 assert got == dense
             else:
                 assert got == list(range(lo, hi))
+
+
+# ------------------------------------------------------- the one-node cap
+def test_one_node_cap_job_smallest_shape(plan):
+    """plan_upper_jobs' `gath && from == top` branch (a cap of one node: the
+    job copies the gathered run root into the cap and the root slot) exists
+    only with one rank, where the last run layer has 4096 values: the tool
+    finds the smallest shape that plans it, 2^12 rows (the smallest sharded
+    shape), layer 3 of 2^15 / 8. tests/test_gpu_sharded.py proves that shape
+    (test_sharded_algorithm_over_rccl_one_rank) against the oracle."""
+    c = plan(2, "logn:0", "onecap", world=1, sharded=True)["onecap"]
+    assert c["logn"] == 12 and c["count"] == 1
+    assert (c["layer"], c["cap"], c["from"], c["to"], c["logLen"], c["lstore"]) == (3, 1, 12, 0, 12, 12)
+    assert (c["wg"], c["nrun"], c["logP"]) == (0, 1, 0)
+    # the same job in the full plan of that shape, and in every larger one-rank shape's last run layer
+    for logn in (12, 13, 18):
+        f = plan(2, "logn:%d" % logn, "fri", world=1, sharded=True)["fri"]
+        caps = [p for p in f["passes"] if p["gath"] and p["from"] == p["logLen"]]
+        assert len(caps) == 1 and caps[0]["count"] == 1 and caps[0]["layer"] == logn + 3 - 12, (logn, caps)
+    # no other world, and no unsharded plan, has it
+    for world in (2, 4, 8):
+        assert plan(2, "logn:0", "onecap", world=world, sharded=True)["onecap"]["logn"] == -1
+    assert plan(2, "logn:0", "onecap")["onecap"]["logn"] == -1

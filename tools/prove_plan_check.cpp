@@ -5,11 +5,14 @@
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -o prove_plan_check tools/prove_plan_check.cpp
 //   ./prove_plan_check TAU RANK WORLD SHARDED USE_DICT WHAT STEP_START...
 //
-// WHAT: a comma list of shape, columns, fri, proof. STEP_START: the nblk + 1
+// WHAT: a comma list of shape, columns, fri, proof, onecap. STEP_START: the nblk + 1
 // block boundaries, or the one word logn:L for the shape of 2^L rows without
 // block boundaries (shape, fri and proof only; the shard's chunks and blocks
 // are not planned). A shape the planner rejects prints {"error": "..."} and
-// exits 2.
+// exits 2. onecap (alone; STEP_START is ignored): the smallest log2(n) of this
+// WORLD / SHARDED whose FRI plan holds a one-node-cap job of plan_upper_jobs
+// (gathered run roots and from == the cap's top level: the job only copies
+// the root), with that job, or logn -1 when no shape up to 2^28 rows has one.
 #include <stdio.h>
 #include <stdlib.h>
 #include <string.h>
@@ -53,6 +56,30 @@ int main(int argc, char** argv) {
   if (strncmp(argv[7], "logn:", 5) == 0) only_logn = atoi(argv[7] + 5);
   else
     for (int i = 7; i < argc; i++) ss.push_back(strtoull(argv[i], nullptr, 10));
+  if (want("onecap")) {
+    for (int logn = 0; logn <= 28; logn++) {
+      try {
+        const ShapePlan s = shape_of_logn(tau, 1, logn, rank, logP, sharded);
+        const FriPlan f = plan_fri(s);
+        size_t cnt = 0, first = 0;
+        for (size_t i = 0; i < f.jobs.size(); i++) {
+          const UpperJob& J = f.jobs[i];
+          const int top = (J.to > 0 && J.to < J.tree.logLen) ? J.to : J.tree.logLen;
+          if (J.gath && J.from == top && !cnt++) first = i;
+        }
+        if (!cnt) continue;
+        const UpperJob& J = f.jobs[first];
+        printf("{\"onecap\": {\"logn\": %d, \"count\": %zu, \"job\": %zu, \"layer\": %d, \"cap\": %d, \"from\": %d, "
+               "\"to\": %d, \"logLen\": %d, \"lstore\": %d, \"wg\": %u, \"nrun\": %llu, \"logP\": %d}}\n",
+               logn, cnt, first, f.job_layer[first], (int)f.job_cap[first], J.from, J.to, J.tree.logLen, J.tree.lstore,
+               J.wg, (unsigned long long)J.nrun, J.logP);
+        return 0;
+      } catch (const PlanError&) {  // a shape this WORLD / SHARDED does not have
+      }
+    }
+    printf("{\"onecap\": {\"logn\": -1}}\n");
+    return 0;
+  }
   try {
     ShapePlan s;
     if (only_logn >= 0) s = shape_of_logn(tau, 1, only_logn, rank, logP, sharded);
