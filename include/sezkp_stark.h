@@ -221,6 +221,18 @@ int32_t sezkp_ctx_dict_plans(const sezkp_ctx* ctx, sezkp_dict_plan_info* out, in
 int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* ctx, uint32_t* cols_rebuilt, uint32_t* cols_reused,
                                    uint64_t* entries_rebuilt);
 
+/* The per-block piecewise columns (win_len, in_off, out_off of every tape)
+ * commit through tables of uniform-subtree hashes. A column whose values over
+ * the device's blocks span fewer values than it has blocks builds one table
+ * unit per value, any other one unit per block; the device chooses per column
+ * and per prove (SEZKP_PW_BY_VALUE=0, read per prove: always per block), and
+ * the proof bytes never depend on it. This reports the last completed prove:
+ * columns keyed by value, columns keyed by block, and the units the former
+ * built (all three 0 before the first prove of an upload). Returns SEZKP_OK,
+ * or SEZKP_E_INVALID for a null argument or while a proof is in flight. */
+int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* ctx, uint32_t* cols_by_value, uint32_t* cols_by_block,
+                                 uint64_t* units_built);
+
 /* ------------------------------------------------ full-trace AIR audit
  * Does the committed trace satisfy the AIR, on every row? The reference
  * verifier recomputes the composition (air.rs:49-136) only on its 30 opened

@@ -89,6 +89,10 @@ __device__ __forceinline__ uint64_t gl_sqr(uint64_t a) { return gl_mul(a, a); }
 __device__ __forceinline__ uint64_t gl_from_i64(int64_t x) {
   return x >= 0 ? (uint64_t)x : GL_P - (uint64_t)(-x);   // |x| < 2^63 << p
 }
+// the signed view of a canonical value: x for x <= p/2, x - p above
+__device__ __forceinline__ int64_t gl_to_i64(uint64_t x) {
+  return x > GL_P / 2 ? -(int64_t)(GL_P - x) : (int64_t)x;
+}
 // a^(p-2) via the 2^32-1 addition chain (72 mul/sqr)
 __device__ __forceinline__ uint64_t gl_pow2k(uint64_t x, int k) {
   for (int i = 0; i < k; i++) x = gl_sqr(x);

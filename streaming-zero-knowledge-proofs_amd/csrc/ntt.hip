@@ -18,6 +18,9 @@
 #include <stdlib.h>
 
 #include <algorithm>
+#include <map>
+#include <mutex>
+#include <tuple>
 
 #include "dev_common.h"
 #include "gl_pow2.h"
@@ -38,6 +41,13 @@ __device__ __forceinline__ uint64_t tw_pow(const NttTables& T, uint64_t e, bool 
 }
 __device__ __forceinline__ uint64_t pow3(const NttTables& T, uint64_t e) {
   return gl_mul(T.p3_hi[e >> T.S], T.p3_lo[e & ((1ULL << T.S) - 1)]);
+}
+// tw_pow(T, i << T.S, inverse) without its product: the exponent's low part is
+// zero and lo[0] = 1, so the factor is one entry of the hi table (the inverse
+// mirrors the index as tw_pow mirrors the exponent)
+__device__ __forceinline__ uint64_t tw_hi(const NttTables& T, uint64_t i, bool inverse) {
+  const uint64_t mask = (1ULL << (T.K - T.S)) - 1;
+  return T.hi[(inverse ? 0 - i : i) & mask];
 }
 
 // slot of coefficient e (= bitrev of the load position k) in the replicated
@@ -405,7 +415,9 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt4(NttPassArgs P) {
   __shared__ uint64_t W[R];
   const int tid = threadIdx.x;
   const NttTables& T = P.tw;
-  for (int x = tid; x < R; x += NTT_THREADS) W[x] = tw_pow(T, (uint64_t)x << (T.K - m), INV);
+  // x << (K - m) has no low part (m <= K - S): with the tables on, a load
+  for (int x = tid; x < R; x += NTT_THREADS)
+    W[x] = P.tw_tab ? tw_hi(T, (uint64_t)x << (T.K - T.S - m), INV) : tw_pow(T, (uint64_t)x << (T.K - m), INV);
   Tile G;
   G.sL = P.sL;
   G.m = m;
@@ -419,6 +431,11 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt4(NttPassArgs P) {
     G.low0 = (G.tile % tiles_per_blk) * NTT_CMAX;
   }
   const int tw_shift = T.K - m - G.sL;
+  // pass twiddle w_{2^(m + sL)}^(low j) of a wide pass with m + sL <= K - S:
+  // one load per element from the pass's own table (pass_twiddles), row j,
+  // column low, so the 16 lanes of a tile row read one 128-B segment as they
+  // do for the data: no chain, no tw_pow
+  const bool pass_tab = !NARROW && P.tw_pass != nullptr;
   const int c = tid & (NTT_CMAX - 1), g = tid / NTT_CMAX;
   // a plain NARROW load stages the tile through the LDS image first
   const bool staged_load = NARROW && !P.dp_rlo && !P.src;
@@ -471,7 +488,15 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt4(NttPassArgs P) {
 #pragma unroll
           for (int r = 0; r < F1; r++) x[r] = gl_mul(x[r], P.out_scale);
         }
-        if (low != 0) {  // pre-twiddle w^(low * (j1 + F2 j2)), j2 = rev(r)
+        if (low != 0 && pass_tab) {  // pre-twiddle w^(low * (j1 + F2 j2)), j2 = rev(r), from the table
+          const int j1 = rev<M2>(u);
+#pragma unroll
+          for (int q = 0; q < F1; q++) {
+            uint64_t f = P.tw_pass[((uint64_t)(j1 + F2 * q) << G.sL) + low];
+            if (scale) f = gl_mul(f, P.out_scale);
+            x[rev<M1>(q)] = gl_mul(x[rev<M1>(q)], f);
+          }
+        } else if (low != 0) {  // the same factors as a chain
           const int j1 = rev<M2>(u);
           uint64_t t = tw_pow(T, (low * (uint64_t)j1) << tw_shift, INV);
           if (scale) t = gl_mul(t, P.out_scale);
@@ -562,7 +587,12 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt4(NttPassArgs P) {
       fft_dif_regs<M1, INV>(y);
       uint64_t low;
       (void)tile_pos(G, q * F1, c, low);
-      if (low != 0) {  // post-twiddle w^(low * (k_lo + F2 k_hi)), k_hi = rev(q')
+      if (low != 0 && pass_tab) {  // post-twiddle w^(low * (k_lo + F2 k_hi)), k_hi = rev(q'), from the table
+        const int klo = rev<M2>(q);
+#pragma unroll
+        for (int kh = 0; kh < F1; kh++)
+          y[rev<M1>(kh)] = gl_mul(y[rev<M1>(kh)], P.tw_pass[((uint64_t)(klo + F2 * kh) << G.sL) + low]);
+      } else if (low != 0) {  // the same factors as a chain
         uint64_t t = tw_pow(T, (low * (uint64_t)rev<M2>(q)) << tw_shift, INV);
         const uint64_t s1 = tw_pow(T, (low * (uint64_t)F2) << tw_shift, INV);
 #pragma unroll
@@ -870,10 +900,62 @@ static bool launch_r8(hipStream_t st, const NttPassArgs& P, bool inverse, unsign
   return false;
 }
 
+// SEZKP_NTT_TW_TABLE=0 (read per launch): k_ntt4 keeps tw_pow and the chains
+static int ntt_tw_table_on() {
+  const char* e = getenv("SEZKP_NTT_TW_TABLE");
+  return !(e && e[0] == '0' && !e[1]);
+}
+
+// The pass twiddles of a wide k_ntt4 pass as a table: entry (j << sL) + low =
+// w_{2^(m + sL)}^(+-low j) for j < 2^m, low < 2^sL. While m + sL <= K - S the
+// exponent (low j) << (K - m - sL) has no low part, so every entry is a copy
+// of one hi entry (exact). Read straight from hi, the 16 lanes of a tile row
+// would fetch 16 entries j apart (a cache line each: the m = 8, sL = 8 pass of
+// a 2^24-point transform measured 94 against 89 us with the chain); in this
+// order they read one 128-B segment, as for the data. At most 2^(K - S)
+// entries (512 KB) per geometry, built on first use and kept for the
+// process, per device; the few geometries a prover's sizes use stay in L2.
+__global__ void __launch_bounds__(NTT_THREADS) k_pass_twiddles(NttTables T, uint64_t* __restrict__ tab, int sL, int m,
+                                                               int inverse) {
+  const uint64_t i = (uint64_t)blockIdx.x * NTT_THREADS + threadIdx.x;
+  if (i >> (sL + m)) return;
+  const uint64_t low = i & ((1ULL << sL) - 1), j = i >> sL;
+  tab[i] = tw_hi(T, (low * j) << (T.K - T.S - m - sL), inverse != 0);
+}
+static const uint64_t* pass_twiddles(hipStream_t st, const NttTables& T, int sL, int m, bool inverse) {
+  static std::mutex mu;
+  static std::map<std::tuple<int, const uint64_t*, int, int, int, int, bool>, uint64_t*> tabs;
+  if (sL < 4 || m + sL > T.K - T.S) return nullptr;
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess) return nullptr;
+  std::lock_guard<std::mutex> lk(mu);
+  const auto key = std::make_tuple(dev, T.hi, T.K, T.S, sL, m, inverse);
+  auto it = tabs.find(key);
+  if (it != tabs.end()) return it->second;
+  // first use: built on the caller's stream and waited for, so that a launch
+  // on any other stream finds it complete. A failure leaves the chain for
+  // this launch (the error is peeked at, not cleared: an earlier one stays
+  // for the caller's own check). The tables live as long as the process, as
+  // the hi / lo tables they copy do.
+  uint64_t* d = nullptr;
+  const uint64_t cnt = 1ULL << (sL + m);
+  if (hipMalloc((void**)&d, cnt * 8) != hipSuccess) return nullptr;
+  hipLaunchKernelGGL(k_pass_twiddles, dim3((unsigned)((cnt + NTT_THREADS - 1) / NTT_THREADS)), dim3(NTT_THREADS), 0, st,
+                     T, d, sL, m, inverse ? 1 : 0);
+  if (hipPeekAtLastError() != hipSuccess || hipStreamSynchronize(st) != hipSuccess) {
+    (void)hipFree(d);
+    return nullptr;
+  }
+  tabs.emplace(key, d);
+  return d;
+}
+
 // launch one pass with the register kernel when its shape allows, else false
 template <bool DIF, bool INV>
-static bool launch_ntt4(hipStream_t st, const NttPassArgs& P, unsigned tiles) {
-  if (P.logC != 4) return false;
+static bool launch_ntt4(hipStream_t st, const NttPassArgs& P0, unsigned tiles) {
+  if (P0.logC != 4) return false;
+  NttPassArgs P = P0;
+  P.tw_tab = ntt_tw_table_on();
   const int skip = P.src ? P.skip : 0;
   if (DIF && skip) return false;
   // sL = 0 passes stage their tile through the LDS image (k_ntt4 NARROW)
@@ -881,8 +963,10 @@ static bool launch_ntt4(hipStream_t st, const NttPassArgs& P, unsigned tiles) {
   do {                                                                                                         \
     if (P.sL == 0)                                                                                           \
       hipLaunchKernelGGL((k_ntt4<DIF, INV, M1, M2, SK, false, true>), dim3(tiles), dim3(NTT_THREADS), 0, st, P); \
-    else                                                                                                       \
+    else {  /* a wide pass the register kernel takes: only here is its twiddle table asked for */            \
+      P.tw_pass = P.tw_tab ? pass_twiddles(st, P.tw, P.sL, P.m, INV) : nullptr;                               \
       hipLaunchKernelGGL((k_ntt4<DIF, INV, M1, M2, SK>), dim3(tiles), dim3(NTT_THREADS), 0, st, P);           \
+    }                                                                                                          \
   } while (0)
   if (P.m > NTT_MMAX) {  // NARROW + in-tile radix-16 (plan_passes_x16)
     // plain passes, or the LDE's DEEP-polynomial first pass (all its stages: no skip)
@@ -1396,6 +1480,8 @@ hipError_t ntt_dit(hipStream_t st, uint64_t* a, int logN, bool inverse, const Nt
     if (deep && fused && i == np - 1 && i > 0 && !inverse &&
         logC == 4 && P.sL >= 4 && (P.m == 8 || P.m == 7)) {
       P.deep_z = deep->z; P.deep_logN = deep->logN; P.deep_logP = deep->logP; P.deep_g = deep->g;
+      P.tw_tab = ntt_tw_table_on();
+      P.tw_pass = P.tw_tab ? pass_twiddles(st, T, P.sL, P.m, false) : nullptr;
       if (P.m == 8)
         hipLaunchKernelGGL((k_ntt4<false, false, 4, 4, 0, true>), dim3((unsigned)tiles), dim3(NTT_THREADS), 0, st, P);
       else

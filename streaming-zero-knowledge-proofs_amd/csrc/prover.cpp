@@ -210,6 +210,13 @@ struct sezkp_ctx {
   bool dict_dirty = false;
   uint32_t dstat_rebuilt = 0, dstat_reused = 0;  // last completed prove (sezkp_ctx_dict_cache_stats)
   uint64_t dstat_entries = 0;
+  // the per-block piecewise columns (kinds 7..9) and, of the last completed
+  // prove, how many keyed their U tables by value and the units those built
+  // (sezkp_ctx_pw_table_stats; TraceDev::pw_stat)
+  std::vector<uint32_t> pw_blk_cols;
+  uint32_t* d_pwstat = nullptr;
+  uint32_t pwstat_by_value = 0;
+  uint64_t pwstat_units = 0;
   void free_dict_cache() {
     if (d_dtabs) (void)hipFree(d_dtabs);
     if (d_dkeys) (void)hipFree(d_dkeys);
@@ -721,13 +728,21 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   tab_units = cp.tab_units;
   d_tmpl = dalloc<ColTemplate>(ncols);
   up(d_tmpl, tm.data(), tm.size());
+  T.pw_lo = dalloc<int64_t>(2 * (size_t)ncols + 2);
+  pw_blk_cols.clear();
+  for (int c = 0; c < ncols; c++)
+    if (tm[c].kind >= 7) pw_blk_cols.push_back((uint32_t)c);
   // column roots, then the guard words ([0] this rank's guard, [8 + r] rank
   // r's guard when sharded): one D2H copy
-  // and behind them the dictionary cache's status words (k_dict_plan)
-  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16 + 2 * dcols.size());
+  // and behind them the dictionary cache's status words (k_dict_plan) and
+  // one word per column for the piecewise tables' form (k_col_tables)
+  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16 + 2 * dcols.size() + ncols);
   d_err = d_colroots + (size_t)ncols * 8;
   d_dstatus = d_err + 16;
+  d_pwstat = d_dstatus + 2 * dcols.size();
+  T.pw_stat = d_pwstat;
   HIP_OR_THROW(hipMemset(d_err, 0, 64));
+  HIP_OR_THROW(hipMemset(d_pwstat, 0, (size_t)ncols * 4));
   d_tabs = dalloc<uint32_t>(cp.tab_nodes * 8 + 8);
   n_tab_cols = (int)cp.tab_cols.size();
   d_tab_cols = dalloc<uint32_t>(cp.tab_cols.size() + 1);
@@ -870,7 +885,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   PL.base = dalloc<uint32_t>(PL.total / 4 + 2);
   h_proof = halloc<uint8_t>(hdr_bytes + PL.total);
   memcpy(h_proof, pp.header.data(), hdr_bytes);
-  h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + 2 * (size_t)n_dict);
+  h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + 2 * (size_t)n_dict + (size_t)ncols);
   d_chal = dalloc<DevChal>(1);
   h_chal = halloc<DevChal>(1);
   d_dict_of = dalloc<uint32_t>((size_t)ncols);
@@ -1467,8 +1482,8 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   // 5.3 against 24.6 us for a warm proof, but 138 against 38 us with the head
   // columns rebuilding and 317 against 104 us for a full rebuild, and a wrong
   // guess at every change of trace: not kept, profiles/dict_cache/README.md.)
-  uint32_t st_rebuilt = 0;
-  uint64_t st_entries = 0;
+  uint32_t st_rebuilt = 0, st_pw_by_value = 0;
+  uint64_t st_entries = 0, st_pw_units = 0;
   const int nguard = sharded ? comm->world : 1;
   auto check_guards = [&](const uint32_t* g_h, int ng) {
     for (int r = 0; r < ng; r++) {
@@ -1581,10 +1596,9 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     rec(3);
     // one copy: the column roots and the guard words stored right behind them
     // (d_err = d_colroots + 8 ncols; sharded, every rank's word at d_err + 8),
-    // and the dictionary cache's status words behind the 16 guard words
-    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots,
-                                n_dict ? (size_t)ncols * 32 + 4 * (16 + 2 * (size_t)n_dict)
-                                       : (size_t)ncols * 32 + 4 * (gofs + nguard),
+    // and the dictionary cache's status words and the piecewise tables'
+    // form words behind the 16 guard words
+    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots, (size_t)ncols * 32 + 4 * (16 + 2 * (size_t)n_dict + (size_t)ncols),
                                 hipMemcpyDeviceToHost, st));
   };
   auto host_1 = [&]() {
@@ -1593,6 +1607,11 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     for (int c = 0; c < n_dict; c++) {
       st_rebuilt += h_small[8 * ncols + 16 + 2 * c];
       st_entries += h_small[8 * ncols + 16 + 2 * c + 1];
+    }
+    for (uint32_t c : pw_blk_cols) {
+      const uint32_t units = h_small[8 * ncols + 16 + 2 * n_dict + c];
+      st_pw_by_value += units != 0;
+      st_pw_units += units;
     }
     std::vector<uint8_t> colroots((const uint8_t*)colroots_h, (const uint8_t*)colroots_h + (size_t)ncols * 32);
     for (int c = 0; c < ncols; c++) memcpy(h_proof + root_pos[c], colroots.data() + 32 * c, 32);
@@ -2047,6 +2066,8 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   dstat_rebuilt = st_rebuilt;
   dstat_reused = (uint32_t)n_dict - st_rebuilt;
   dstat_entries = st_entries;
+  pwstat_by_value = st_pw_by_value;
+  pwstat_units = st_pw_units;
   return out;
 }
 
@@ -2385,6 +2406,17 @@ int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* cctx, uint32_t* cols_rebuilt
   *cols_rebuilt = have ? ctx->dstat_rebuilt : 0;
   *cols_reused = have ? ctx->dstat_reused : 0;
   *entries_rebuilt = have ? ctx->dstat_entries : 0;
+  return SEZKP_OK;
+}
+int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* cctx, uint32_t* cols_by_value, uint32_t* cols_by_block,
+                                 uint64_t* units_built) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || !cols_by_value || !cols_by_block || !units_built) return SEZKP_E_INVALID;
+  if (ctx->busy()) return SEZKP_E_INVALID;  // the counts are rewritten by the proof in flight
+  const bool have = ctx->loaded && ctx->have_plans;
+  *cols_by_value = have ? ctx->pwstat_by_value : 0;
+  *cols_by_block = have ? (uint32_t)ctx->pw_blk_cols.size() - ctx->pwstat_by_value : 0;
+  *units_built = have ? ctx->pwstat_units : 0;
   return SEZKP_OK;
 }
 int32_t sezkp_ctx_comm_stats(const sezkp_ctx* ctx, sezkp_comm_stat* out, int32_t max) {

@@ -55,6 +55,12 @@ struct NttPassArgs {
   // outputs share 128-B lines and stores them transposed into natural order
   // (ntt.hip gather_to_lds / lds_to_transposed)
   int nat_tr;
+  // k_ntt4, twiddles as loads (both off with SEZKP_NTT_TW_TABLE=0): tw_tab:
+  // W[] from tw.hi alone instead of tw_pow; tw_pass: the pass twiddles
+  // w_{2^(m + sL)}^(low j) at [(j << sL) + low] for a wide pass with
+  // m + sL <= K - S (ntt.hip pass_twiddles), null = the multiplication chain
+  int tw_tab;
+  const uint64_t* tw_pass;
 };
 // DEEP division y_i / (3 w_N^(g + P i) - z) fused into the LDE's last pass
 struct DeepFuse {
@@ -135,7 +141,16 @@ struct TraceDev {
   uint8_t* row_flags;         // [n]   bit0 first, bit1 last (derived)
   int32_t* head;              // [tau][n] post-move head (derived; block-local; k_expand rejects |head| >= 2^31)
   int64_t* head_rng;          // [tau][nblk][2] per-block min / max of head (derived by k_expand)
+  // written by k_col_tables in every proof for the per-block columns (kinds
+  // 7..9). pw_lo[2 col]: the smallest block value (signed view) when the
+  // column's U tables are keyed by value - lo, PW_BY_BLOCK when keyed by
+  // block; pw_lo[2 col + 1]: the last unit a reader may take (values - 1, or
+  // nblk - 1 by block). pw_stat[col]: units built by value, 0 by block (comes
+  // home with the column roots: sezkp_ctx_pw_table_stats)
+  int64_t* pw_lo;
+  uint32_t* pw_stat;
 };
+constexpr int64_t PW_BY_BLOCK = INT64_MIN;
 
 // Per-row constraint sums of the composition (k_compose_terms): everything
 // of C(i) that does not depend on the transcript, summed over the tapes

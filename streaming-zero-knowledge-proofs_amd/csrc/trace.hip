@@ -339,12 +339,35 @@ __device__ __forceinline__ void hash4_labeled(const ColTemplate& ct, const uint6
 // -------------------------------------------------------- column tables
 // grid (work/256, table columns). Leaf-table columns: entry e -> labelled leaf
 // of the raw value e (i8 reinterpreted, u8, u16). Piecewise columns: one lane
-// per run value computes U_0..U_10 with U_0 = leaf(v), U_{l+1} = H(U_l || U_l),
-// the root of a 2^l-row subtree whose rows all hold v.
+// per table unit computes U_0..U_10 with U_0 = leaf(v), U_{l+1} = H(U_l || U_l),
+// the root of a 2^l-row subtree whose rows all hold v. U_l(v) depends on the
+// label and on v only, and the per-block values (win_len, in_off, out_off)
+// repeat from block to block, so a per-block column whose signed range over
+// this rank's blocks [lo, hi] has fewer values than the rank has blocks keys
+// its units by value: unit v - lo, hi - lo + 1 lanes instead of one per block
+// (T.pw_lo[2 col] = lo, [2 col + 1] = hi - lo for the readers, pw_unit). A wider range keeps one unit
+// per block (PW_BY_BLOCK): never more lanes than blocks, and the slot's nblk
+// units hold either form. Every workgroup of the column takes the range itself
+// (blk_cnt loads of an L2-resident table; no launch and no order between
+// workgroups).
+__device__ __forceinline__ const uint64_t* pw_block_values(const TraceDev& T, const ColTemplate& ct) {
+  const uint64_t* tab = ct.kind == 7 ? T.blk_winlen : (ct.kind == 8 ? T.blk_offin : T.blk_offout);
+  return tab + (uint64_t)ct.tape * T.nblk;
+}
+// table unit of block k's value: bv = pw_block_values, lo = T.pw_lo[2 col].
+// The readers refuse a unit above T.pw_lo[2 col + 1], the last one built: a
+// block whose value lies outside the range the table was built for.
+__device__ __forceinline__ uint32_t pw_unit(const uint64_t* __restrict__ bv, int64_t lo, uint32_t k) {
+  if (lo == PW_BY_BLOCK) return k;
+  const uint64_t u = (uint64_t)gl_to_i64(bv[k]) - (uint64_t)lo;
+  return u > 0xffffffffull ? 0xffffffffu : (uint32_t)u;
+}
 __global__ void __launch_bounds__(TR_THREADS) k_col_tables(TraceDev T, const ColTemplate* __restrict__ tmpl,
                                                            const uint32_t* __restrict__ cols, uint32_t* __restrict__ tabs,
-                                                           uint32_t blk_lo, uint32_t blk_cnt) {
-  const ColTemplate ct = tmpl[cols[blockIdx.y]];
+                                                           uint32_t blk_lo, uint32_t blk_cnt, int by_value_ok) {
+  __shared__ int64_t s_rng[2][TR_THREADS / 64];
+  const uint32_t col = cols[blockIdx.y];
+  const ColTemplate ct = tmpl[col];
   uint64_t i = (uint64_t)blockIdx.x * TR_THREADS + threadIdx.x;
   uint32_t h[8];
   if (kind_has_leaf_table(ct.kind)) {
@@ -354,15 +377,51 @@ __global__ void __launch_bounds__(TR_THREADS) k_col_tables(TraceDev T, const Col
     node_store(tabs + 8 * (ct.tab + i), h);
     return;
   }
-  // per-block constants: only blocks [blk_lo, blk_lo + blk_cnt) (this rank's rows)
-  const bool flags = ct.kind == 1 || ct.kind == 2;
-  if (flags ? i >= 2 : i >= blk_cnt) return;
-  if (!flags) i += blk_lo;
   uint64_t v;
-  if (ct.kind == 1 || ct.kind == 2) v = i;
-  else {
-    const uint64_t* tab = ct.kind == 7 ? T.blk_winlen : (ct.kind == 8 ? T.blk_offin : T.blk_offout);
-    v = tab[(uint64_t)ct.tape * T.nblk + i];
+  if (ct.kind == 1 || ct.kind == 2) {
+    if (i >= 2) return;
+    v = i;
+  } else {
+    // per-block constants: only blocks [blk_lo, blk_lo + blk_cnt) (this rank's rows)
+    if (blockIdx.x && (uint64_t)blockIdx.x * TR_THREADS >= blk_cnt) return;  // no unit in either form
+    const uint64_t* bv = pw_block_values(T, ct) + blk_lo;
+    int64_t mn = INT64_MAX, mx = INT64_MIN;
+    for (uint32_t j = threadIdx.x; j < blk_cnt; j += TR_THREADS) {
+      const int64_t s = gl_to_i64(bv[j]);
+      mn = s < mn ? s : mn;
+      mx = s > mx ? s : mx;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) {
+      const int64_t a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
+      mn = a < mn ? a : mn;
+      mx = b > mx ? b : mx;
+    }
+    if ((threadIdx.x & 63) == 0) {
+      s_rng[0][threadIdx.x >> 6] = mn;
+      s_rng[1][threadIdx.x >> 6] = mx;
+    }
+    __syncthreads();
+#pragma unroll
+    for (int w = 0; w < TR_THREADS / 64; w++) {
+      mn = s_rng[0][w] < mn ? s_rng[0][w] : mn;
+      mx = s_rng[1][w] > mx ? s_rng[1][w] : mx;
+    }
+    const uint64_t span = (uint64_t)mx - (uint64_t)mn;  // values - 1 (blk_cnt > 0)
+    const bool by_value = by_value_ok && blk_cnt && span < blk_cnt;
+    if (i == 0) {
+      T.pw_lo[2 * col] = by_value ? mn : PW_BY_BLOCK;
+      T.pw_lo[2 * col + 1] = by_value ? (int64_t)span : (int64_t)T.nblk - 1;
+      T.pw_stat[col] = by_value ? (uint32_t)span + 1 : 0;
+    }
+    if (by_value) {
+      if (i > span) return;
+      v = gl_from_i64(mn + (int64_t)i);
+    } else {
+      if (i >= blk_cnt) return;
+      v = bv[i];
+      i += blk_lo;
+    }
   }
   leaf_labeled_rt(ct, v, h);
   uint32_t* o = tabs + 8 * (ct.tab + i * U_LEVELS);
@@ -508,6 +567,10 @@ __global__ void __launch_bounds__(PW_THREADS) k_col_commit_pw(TraceDev T, const 
   const uint64_t ch = chunks[item % nchunks];
   const uint32_t kind = tmpl[c].kind;
   const uint32_t* U = tabs + 8 * tmpl[c].tab;
+  const bool per_blk = kind >= 7;  // win_len / in_off / out_off: units by value or by block (pw_unit)
+  const uint64_t* bv = per_blk ? pw_block_values(T, tmpl[c]) : nullptr;
+  const int64_t vlo = per_blk ? T.pw_lo[2 * c] : PW_BY_BLOCK;
+  const uint32_t ulast = per_blk ? (uint32_t)T.pw_lo[2 * c + 1] : T.nblk - 1;
   const uint64_t n = T.n;
   const uint64_t cl = n < 1024 ? n : 1024;
   const uint64_t c0 = ch << COL_CHUNK_LOG2, c1 = c0 + cl;
@@ -524,7 +587,8 @@ __global__ void __launch_bounds__(PW_THREADS) k_col_commit_pw(TraceDev T, const 
     const uint64_t pe = be < c1 ? be : c1;
     // sub-piece [row, cut) holding one value u (table index)
     uint64_t cut = pe;
-    uint32_t u = k;
+    uint32_t u = per_blk ? pw_unit(bv, vlo, k) : k;
+    if (u > ulast) { atomicOr(err, 4u); return; }
     if (kind == 1) { u = row == bs ? 1u : 0u; cut = row == bs ? row + 1 : pe; }
     else if (kind == 2) { u = row + 1 == be ? 1u : 0u; cut = (row + 1 < be && pe == be) ? be - 1 : pe; }
     while (row < cut) {
@@ -1227,9 +1291,12 @@ __device__ __forceinline__ void lane_tree_pf(const Prov& P, uint32_t (&h)[8]) {
 // the run pieces of k_col_commit_pw (maximal aligned dyadic intervals, U_l
 // lookups) merged on this lane's LDS stack. False if the stack overflows or
 // the block table is inconsistent (the commitment flags those chunks).
-__device__ __forceinline__ bool pw_range_hash(const TraceDev& T, uint32_t kind, const uint32_t* __restrict__ U,
-                                              uint64_t r0, int lw, uint32_t (*stk)[8][64], int slot,
-                                              uint32_t (&out)[8]) {
+__device__ __forceinline__ bool pw_range_hash(const TraceDev& T, const ColTemplate& ct, int64_t vlo, uint32_t ulast,
+                                              const uint32_t* __restrict__ U, uint64_t r0, int lw,
+                                              uint32_t (*stk)[8][64], int slot, uint32_t (&out)[8]) {
+  const uint32_t kind = ct.kind;
+  const bool per_blk = kind >= 7;
+  const uint64_t* bv = per_blk ? pw_block_values(T, ct) : nullptr;
   const uint64_t c1 = r0 + (1ULL << lw);
   uint64_t lvpack = 0;
   int sp = 0;
@@ -1241,7 +1308,8 @@ __device__ __forceinline__ bool pw_range_hash(const TraceDev& T, uint32_t kind, 
     if (be <= row) { k++; continue; }
     const uint64_t pe = be < c1 ? be : c1;
     uint64_t cut = pe;
-    uint32_t u = k;
+    uint32_t u = per_blk ? pw_unit(bv, vlo, k) : k;
+    if (u > ulast) return false;
     if (kind == 1) { u = row == bs ? 1u : 0u; cut = row == bs ? row + 1 : pe; }
     else if (kind == 2) { u = row + 1 == be ? 1u : 0u; cut = (row + 1 < be && pe == be) ? be - 1 : pe; }
     while (row < cut) {
@@ -1376,7 +1444,8 @@ __global__ void __launch_bounds__(TR_THREADS) k_col_open(TraceDev T, const ColTe
     if (tid < logcl) {
       uint32_t h[8];
       const uint64_t rs = start + (((in >> tid) ^ 1) << tid);
-      if (pw_range_hash(T, ct.kind, tabs + 8 * (uint64_t)ct.tab, rs, tid,
+      if (pw_range_hash(T, ct, ct.kind >= 7 ? T.pw_lo[2 * c] : PW_BY_BLOCK,
+                        ct.kind >= 7 ? (uint32_t)T.pw_lo[2 * c + 1] : T.nblk - 1, tabs + 8 * (uint64_t)ct.tab, rs, tid,
                         reinterpret_cast<uint32_t(*)[8][64]>(&lds[0][0]), tid, h)) {
 #pragma unroll
         for (int w = 0; w < 8; w++) o[18 + 8 * tid + w] = h[w];
@@ -1896,8 +1965,11 @@ hipError_t launch_col_tables(hipStream_t st, const TraceDev& T, const ColTemplat
   if (n_tab_cols == 0) return hipSuccess;
   if ((uint64_t)blk_lo + blk_cnt > T.nblk) return hipErrorInvalidValue;
   const unsigned gx = (unsigned)((max_units + TR_THREADS - 1) / TR_THREADS);
+  // SEZKP_PW_BY_VALUE=0 (read per proof): every per-block column keeps one unit per block
+  const char* bv = getenv("SEZKP_PW_BY_VALUE");
+  const int by_value_ok = !(bv && bv[0] == '0' && !bv[1]);
   hipLaunchKernelGGL(k_col_tables, dim3(gx, n_tab_cols), dim3(TR_THREADS), 0, st, T, d_tmpl, d_tab_cols, tabs, blk_lo,
-                     blk_cnt);
+                     blk_cnt, by_value_ok);
   return hipGetLastError();
 }
 static hipError_t dict_shape_ok(const TraceDev& T, uint64_t row0, uint64_t nrows) {

@@ -36,7 +36,7 @@ EXPORTS = [
     "sezkp_fs_xof", "sezkp_ctx_upload_rows", "sezkp_shard_rows", "sezkp_blocks_decode_jsonl_meta",
     "sezkp_blocks_line_offsets", "sezkp_manifest_leaf_hashes", "sezkp_merkle_root_of_leaves",
     "sezkp_ctx_create_sharded_solo", "sezkp_blocks_decode_jsonl_lines", "sezkp_ctx_dict_plans",
-    "sezkp_ctx_air_audit", "sezkp_stark_v1_air_audit", "sezkp_ctx_dict_cache_stats",
+    "sezkp_ctx_air_audit", "sezkp_stark_v1_air_audit", "sezkp_ctx_dict_cache_stats", "sezkp_ctx_pw_table_stats",
     "sezkp_ctx_verify_batch", "sezkp_stark_v1_verify_batch", "sezkp_ctx_verify_times",
 ]
 
@@ -155,6 +155,8 @@ def _load():
     L.sezkp_ctx_dict_plans.argtypes = [C.c_void_p, C.POINTER(DictPlanInfo), C.c_int32]
     L.sezkp_ctx_dict_cache_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                              C.POINTER(C.c_uint64)]
+    L.sezkp_ctx_pw_table_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                           C.POINTER(C.c_uint64)]
     L.sezkp_gl_ntt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
     L.sezkp_gl_coset_lde_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]

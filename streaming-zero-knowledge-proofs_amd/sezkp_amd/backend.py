@@ -377,6 +377,16 @@ class ProverContext:
             raise SezkpError(rc, "dict_cache_stats: a proof is in flight on this context (or the context is closed)")
         return {"cols_rebuilt": rebuilt.value, "cols_reused": reused.value, "entries_rebuilt": entries.value}
 
+    def pw_table_stats(self) -> dict:
+        """The per-block piecewise columns' table form in the last completed
+        prove: {cols_by_value, cols_by_block, units_built}
+        (sezkp_ctx_pw_table_stats; all 0 before the first prove of an upload)."""
+        by_value, by_block, units = C.c_uint32(0), C.c_uint32(0), C.c_uint64(0)
+        rc = lib.sezkp_ctx_pw_table_stats(self._h, C.byref(by_value), C.byref(by_block), C.byref(units))
+        if rc < 0:
+            raise SezkpError(rc, "pw_table_stats: a proof is in flight on this context (or the context is closed)")
+        return {"cols_by_value": by_value.value, "cols_by_block": by_block.value, "units_built": units.value}
+
     def dist_ntt(self, local, scratch=None, inverse: bool = False, sync: bool = True):
         """Distributed four-step NTT of n = world * local.numel() points, in
         place on `local` (a device u64/i64 tensor; layouts in sezkp_stark.h,

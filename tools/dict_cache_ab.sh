@@ -11,16 +11,25 @@
 #   ab/                    alternating plain bench.py runs: parent, new, new with SEZKP_DICT_CACHE=0
 #   full/                  alternating bench.py --full runs: parent, new
 # Each step has its own time limit; the first failure ends the script.
+# The same A/B serves any change that has an off switch:
+#   SEZKP_AB_OUT=<dir>       output directory (default out/dict_cache)
+#   SEZKP_AB_OFF=<VAR=value> the third headline arm's switch (default SEZKP_DICT_CACHE=0)
+#   SEZKP_AB_STEPS="prof ab full"  the steps to run (default all three)
 set -euo pipefail
 export TMPDIR=/tmp
 ROOT=$PWD
 PARENT=$(cd "$1" && pwd)
 R=${2:-3}
 RF=${3:-3}
-O=$ROOT/out/dict_cache
+O=${SEZKP_AB_OUT:-$ROOT/out/dict_cache}
+OFF=${SEZKP_AB_OFF:-SEZKP_DICT_CACHE=0}
+STEPS=${SEZKP_AB_STEPS:-prof ab full}
 mkdir -p $O/ab $O/full
+O=$(cd $O && pwd)
+want() { case " $STEPS " in *" $1 "*) return 0;; *) return 1;; esac; }
 P1="python3 bench.py --full --inflight 1 --no-cpu-baseline --no-configs --no-worst-case --no-host-rows --no-sharded --dntt-log-n 0"
 for arm in parent new; do
+  want prof || break
   if [ $arm = parent ]; then cd $PARENT; else cd $ROOT; fi
   mkdir -p $O/prof_$arm $O/pmc_$arm $O/overlap_$arm
   timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof_$arm/trace -o run -- \
@@ -49,24 +58,28 @@ print((a - t0) / 1e6, (b - t0) / 1e6, sum(1 for s, e in r if e and a <= s < b))"
   cd $ROOT
 done
 for i in $(seq 1 $R); do
+  want ab || break
   cd $PARENT
   timeout -k 10 200 python3 bench.py > $O/ab/parent_$i.json 2> $O/ab/parent_$i.err
   cd $ROOT
   timeout -k 10 200 python3 bench.py > $O/ab/new_$i.json 2> $O/ab/new_$i.err
-  SEZKP_DICT_CACHE=0 timeout -k 10 200 python3 bench.py > $O/ab/new_cache_off_$i.json 2> $O/ab/new_cache_off_$i.err
+  env $OFF timeout -k 10 200 python3 bench.py > $O/ab/new_cache_off_$i.json 2> $O/ab/new_cache_off_$i.err
 done
 for i in $(seq 1 $RF); do
+  want full || break
   cd $PARENT
   timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --dump-outputs $O/full/dump_parent > $O/full/parent_$i.json 2> $O/full/parent_$i.err
   cd $ROOT
   timeout -k 10 400 python3 bench.py --full --no-cpu-baseline --dump-outputs $O/full/dump_new > $O/full/new_$i.json 2> $O/full/new_$i.err
 done
-n=0
-for f in $O/full/dump_parent/*; do
-  cmp $f $O/full/dump_new/$(basename $f)
-  n=$((n + 1))
-done
-echo "dumped proofs identical: $n files" > $O/full/dumped_proofs_compare.txt
-python3 tools/dict_cache_report.py $O/ab > $O/ab/headline_ab.txt
-python3 tools/dict_cache_report.py --full $O/full > $O/full/full_ab.txt
+if want full; then
+  n=0
+  for f in $O/full/dump_parent/*; do
+    cmp $f $O/full/dump_new/$(basename $f)
+    n=$((n + 1))
+  done
+  echo "dumped proofs identical: $n files" > $O/full/dumped_proofs_compare.txt
+  python3 tools/dict_cache_report.py --full $O/full > $O/full/full_ab.txt
+fi
+if want ab; then python3 tools/dict_cache_report.py --off-label "$OFF" $O/ab > $O/ab/headline_ab.txt; fi
 echo "dict_cache_ab done"

@@ -5,7 +5,10 @@ SEZKP_DICT_CACHE=0, and the project's bar for a gain: every pair has the new
 arm ahead AND the mean gain exceeds the largest difference between two runs
 of one arm in the session.
 
-    python3 tools/dict_cache_report.py <ab dir>
+    python3 tools/dict_cache_report.py [--off-label VAR=value] <ab dir>
+
+--off-label names the third arm's switch when the A/B ran with another one
+(tools/dict_cache_ab.sh, SEZKP_AB_OFF).
 """
 import glob
 import json
@@ -35,19 +38,19 @@ def verdict(name, new, base):
           + ("a gain by the project's bar" if every and mean_gain > spread else "NOT a gain by the project's bar"))
 
 
-def main(d):
+def main(d, off_label="SEZKP_DICT_CACHE=0"):
     par, new, off = values(d, "parent"), values(d, "new"), values(d, "new_cache_off")
     print("value, 1e9 field-elements/s (plain `python bench.py`, 200 steps, 3 proofs in flight), runs alternating")
-    print("pair   parent      new  new, SEZKP_DICT_CACHE=0")
+    print(f"pair   parent      new  new, {off_label}")
     for i in sorted(new):
         print(f"{i:4d}  {par.get(i, float('nan')):7.3f}  {new[i]:7.3f}  {off.get(i, float('nan')):7.3f}")
-    for name, a in (("parent", par), ("new", new), ("cache off", off)):
+    for name, a in (("parent", par), ("new", new), ("switch off", off)):
         if a:
             print(f"{name:10s} mean {sum(a.values()) / len(a):.3f}  min {min(a.values()):.3f}  max {max(a.values()):.3f}")
     if par:
         verdict("new vs parent", new, par)
     if off:
-        verdict("new vs new with SEZKP_DICT_CACHE=0", new, off)
+        verdict(f"new vs new with {off_label}", new, off)
 
 
 FULL_VIEWS = (  # name, path in the bench line, higher is better
@@ -101,5 +104,7 @@ def full(d):
 if __name__ == "__main__":
     if sys.argv[1] == "--full":
         full(sys.argv[2])
+    elif sys.argv[1] == "--off-label":
+        main(sys.argv[3], sys.argv[2])
     else:
         main(sys.argv[1])
