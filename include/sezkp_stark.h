@@ -221,6 +221,40 @@ int32_t sezkp_ctx_dict_plans(const sezkp_ctx* ctx, sezkp_dict_plan_info* out, in
 int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* ctx, uint32_t* cols_rebuilt, uint32_t* cols_reused,
                                    uint64_t* entries_rebuilt);
 
+/* The wide head ladder. A head column with a delta plan keeps, across the
+ * proofs of one context, a table of 8-row groups keyed by value: (first head,
+ * 7 moves) over a span of heads [origin, origin + span) and the tape's move
+ * range, span * dR^7 entries (at most SEZKP_HEAD_WIDE_CAP, default 2^19, read
+ * per prove). The first prove after anything the dictionary tables depend on
+ * has changed (see above) builds nothing; the next one builds the ladder over
+ * the last completed prove's head range widened by 8 values on each side, and
+ * later proves reuse it. A group the ladder does not cover (a block starting
+ * in its rows 1..7, a first head outside the span) is committed from the
+ * 4-row groups as before, so the proof bytes never depend on the ladder; a
+ * prove in which more than 1/64 of the groups left the span makes the next
+ * one rebuild the ladder over both ranges. SEZKP_HEAD_WIDE=0 (read per prove)
+ * commits every head column from the 4-row groups.
+ * This reports, per head dictionary column and for the last completed prove:
+ * the ladder in place (span 0: none), the column's head range size seen, the
+ * entries that prove built (0 when it reused the ladder), and the 8-row
+ * groups it took from the ladder and those it did not. Returns the number of
+ * records written (0 before the first prove of an upload), SEZKP_E_INVALID
+ * for a bad argument or while a proof is in flight. */
+typedef struct sezkp_head_wide_info {
+  uint32_t col;    /* column index (commitment order) */
+  uint32_t tape;
+  int64_t origin;  /* first head value of the span */
+  uint32_t span;   /* head values covered (0: no ladder in place) */
+  uint32_t dR;     /* move values covered */
+  uint64_t R;      /* the column's head range size in this prove */
+  uint64_t entries_built;       /* ladder entries this prove built, all levels */
+  uint64_t groups_wide;         /* 8-row groups taken from the ladder */
+  uint64_t groups_fallback;     /* 8-row groups committed from 4-row groups instead */
+  uint64_t groups_out_of_span;  /* ... of those, for a head or move outside the ladder */
+  uint64_t table_bytes;         /* device memory held for this column's ladder */
+} sezkp_head_wide_info;
+int32_t sezkp_ctx_head_wide_stats(const sezkp_ctx* ctx, sezkp_head_wide_info* out, int32_t max);
+
 /* The per-block piecewise columns (win_len, in_off, out_off of every tape)
  * commit through tables of uniform-subtree hashes. A column whose values over
  * the device's blocks span fewer values than it has blocks builds one table

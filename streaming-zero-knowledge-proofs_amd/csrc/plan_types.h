@@ -68,6 +68,12 @@ SEZKP_HD inline bool kind_dict(uint32_t kind) { return kind == 0 || (kind >= 3 &
 constexpr int DICT_LANE_LOG = 6;  // rows per lane of the dictionary commitment (level-6 nodes)
 constexpr int DLEV_NODES = 30;
 constexpr uint32_t NO_DICT = 0xFFFFFFFFu;
+// Status words per dictionary column for the wide head ladder, behind the
+// piecewise form words (written by k_dict_plan and k_col_commit_dict, home
+// with the column roots): [0,1] lo, [2,3] hi (i64), [4] mlo, [5] mhi (i32),
+// [6] delta plan, then the 8-row groups taken [7] from L3, [8] through the
+// 4-row nodes for a block start, [9] the same for a head or move outside
+constexpr int HW_STAT_WORDS = 10;
 constexpr int OPEN_REQ_WORDS = 5;  // column, row lo, row hi, ordinal, dictionary index
 
 constexpr int LSTORE_FRI = 6;

@@ -454,4 +454,102 @@ inline ProofPlan plan_proof(const ShapePlan& s, const std::vector<std::string>& 
   return p;
 }
 
+// ------------------------------------------------------ wide head ladder
+// The host side of the persistent 8-row head tables (HeadWideDev,
+// sezkp_internal.h): per head column, when the ladder is built, kept,
+// re-spanned and dropped. The entry of (first head, 7 moves) depends on the
+// column's label and on those values only, so the ladder is keyed by value
+// over a span [olo, olo + span) of heads and a range [dmin, dmin + dR) of
+// moves, and lives as long as the dictionary epoch does.
+//  - The first proof of an epoch builds nothing: a one-shot proof would hash
+//    span dR^7 entries to save fewer compressions.
+//  - From the second proof on the span is the last completed proof's head
+//    range widened by HEAD_WIDE_MARGIN values on each side (head ranges of
+//    one machine shape move by a few values from trace to trace; a walk of
+//    512 steps moves its extremes by less than 8 in most redraws, and a group
+//    outside the span only takes the 4-row path), while span dR^7 <= cap.
+//  - A proof whose groups left the span in more than 1 / HEAD_WIDE_RESPAN of
+//    all groups re-spans the ladder at the next proof: to the union of the
+//    old span and the new range when that fits the cap (so two alternating
+//    traces settle after one rebuild), else to the new range alone.
+constexpr uint32_t HEAD_WIDE_CAP_DEFAULT = 1u << 19;  // L3 entries per column (SEZKP_HEAD_WIDE_CAP)
+constexpr uint32_t HEAD_WIDE_CAP_MAX = 1u << 24;      // the commit indexes L3 in 32 bits
+constexpr int64_t HEAD_WIDE_MARGIN = 8;
+constexpr uint64_t HEAD_WIDE_RESPAN = 64;
+
+// what a completed proof reports of one head column (the status words)
+struct HeadWideObs {
+  int64_t lo = 0, hi = -1;    // head range on this device's rows
+  int64_t mlo = 0, mhi = -1;  // its tape's move range
+  uint32_t delta = 0;         // the column's plan is a delta plan
+  uint32_t wide = 0, fb_start = 0, fb_span = 0;  // 8-row groups: from L3, fallen back at a block start, outside the span
+};
+struct HeadWideCol {
+  uint64_t epoch = 0;  // epoch of the ladder in place (0: none)
+  int64_t olo = 0, dmin = 0;
+  uint32_t span = 0, dR = 0;
+  uint64_t seen_epoch = 0;  // epoch of `seen`
+  HeadWideObs seen;
+  bool respan = false;
+};
+struct HeadWideDecision {
+  bool use = false;    // the commit reads the ladder
+  bool build = false;  // ... after this proof has built it
+  uint64_t l3_entries = 0, low_entries = 0;  // of the ladder in place or to build
+};
+// entries of L3 and of the lower levels L0 | L1 | L2 over the widened value range
+inline bool head_wide_sizes(uint64_t span, uint64_t dR, int64_t dmin, uint64_t cap, uint64_t& l3, uint64_t& low) {
+  if (span == 0 || dR == 0 || dR > 256) return false;
+  uint64_t p7 = 1;
+  for (int i = 0; i < 7; i++) p7 *= dR;  // <= 2^56
+  if (cap > HEAD_WIDE_CAP_MAX) cap = HEAD_WIDE_CAP_MAX;
+  if (p7 > cap || span > cap / p7) return false;
+  const int64_t dmax = dmin + (int64_t)dR - 1;
+  const int64_t neg = dmin < 0 ? dmin : 0, pos = dmax > 0 ? dmax : 0;
+  const uint64_t sw = span + 7 * (uint64_t)(pos - neg);
+  l3 = span * p7;
+  low = sw * (1 + dR + dR * dR * dR);
+  return true;
+}
+inline HeadWideDecision head_wide_decide(HeadWideCol& c, uint64_t epoch, uint64_t cap) {
+  HeadWideDecision d;
+  if (c.epoch == epoch && !c.respan) {  // in place
+    d.use = head_wide_sizes(c.span, c.dR, c.dmin, cap, d.l3_entries, d.low_entries);
+    if (!d.use) c.epoch = 0;  // the cap was lowered: the ladder is dropped
+    return d;
+  }
+  const HeadWideObs& s = c.seen;
+  if (c.seen_epoch != epoch || !s.delta || s.lo > s.hi || s.mlo > s.mhi) {
+    if (c.epoch != epoch) c.epoch = 0;
+    return d;
+  }
+  int64_t lo = s.lo - HEAD_WIDE_MARGIN, hi = s.hi + HEAD_WIDE_MARGIN, mlo = s.mlo, mhi = s.mhi;
+  if (c.epoch == epoch) {  // a re-span: the union with the old span, if that qualifies
+    const int64_t ulo = std::min(lo, c.olo), uhi = std::max(hi, c.olo + (int64_t)c.span - 1);
+    const int64_t umlo = std::min(mlo, c.dmin), umhi = std::max(mhi, c.dmin + (int64_t)c.dR - 1);
+    uint64_t a, b;
+    if (head_wide_sizes((uint64_t)(uhi - ulo) + 1, (uint64_t)(umhi - umlo) + 1, umlo, cap, a, b)) {
+      lo = ulo; hi = uhi; mlo = umlo; mhi = umhi;
+    }
+  }
+  c.respan = false;
+  c.epoch = 0;
+  if (!head_wide_sizes((uint64_t)(hi - lo) + 1, (uint64_t)(mhi - mlo) + 1, mlo, cap, d.l3_entries, d.low_entries))
+    return d;
+  c.epoch = epoch;
+  c.olo = lo;
+  c.span = (uint32_t)(hi - lo + 1);
+  c.dmin = mlo;
+  c.dR = (uint32_t)(mhi - mlo + 1);
+  d.use = d.build = true;
+  return d;
+}
+// after a proof of `epoch` has completed
+inline void head_wide_observe(HeadWideCol& c, uint64_t epoch, const HeadWideObs& o) {
+  c.seen_epoch = epoch;
+  c.seen = o;
+  const uint64_t groups = (uint64_t)o.wide + o.fb_start + o.fb_span;
+  if (c.epoch == epoch && o.delta && (uint64_t)o.fb_span * HEAD_WIDE_RESPAN > groups) c.respan = true;
+}
+
 }  // namespace sezkp

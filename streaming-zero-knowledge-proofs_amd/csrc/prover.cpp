@@ -217,11 +217,31 @@ struct sezkp_ctx {
   uint32_t* d_pwstat = nullptr;
   uint32_t pwstat_by_value = 0;
   uint64_t pwstat_units = 0;
+  // The wide head ladders (HeadWideDev) sit beside the dictionary tables:
+  // one record per dictionary column in d_hw (written only by a proof that
+  // builds a ladder), the ladders in d_hwtabs (allocated by the first such
+  // proof, regrown when a re-span needs more), the host's state in hw_cols
+  // (prove_plan.h) and the last completed prove's report in hw_stats
+  // (sezkp_ctx_head_wide_stats). d_hwstat: the status words, behind d_pwstat.
+  HeadWideDev* d_hw = nullptr;
+  uint32_t* d_hwtabs = nullptr;
+  uint64_t hwtabs_nodes = 0;
+  uint32_t* d_hwstat = nullptr;
+  std::vector<HeadWideCol> hw_cols;
+  std::vector<HeadWideDev> hw_recs;
+  std::vector<sezkp_head_wide_info> hw_stats;
   void free_dict_cache() {
     if (d_dtabs) (void)hipFree(d_dtabs);
     if (d_dkeys) (void)hipFree(d_dkeys);
+    if (d_hw) (void)hipFree(d_hw);
+    if (d_hwtabs) (void)hipFree(d_hwtabs);
     d_dtabs = nullptr;
     d_dkeys = nullptr;
+    d_hw = nullptr;
+    d_hwtabs = nullptr;
+    hwtabs_nodes = 0;
+    hw_cols.clear();
+    hw_recs.clear();
     dict_cache_cols = ~(size_t)0;
   }
   uint32_t* d_dlev = nullptr;        // dictionary columns' chunk levels 6..9 (openings)
@@ -736,10 +756,12 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   // r's guard when sharded): one D2H copy
   // and behind them the dictionary cache's status words (k_dict_plan) and
   // one word per column for the piecewise tables' form (k_col_tables)
-  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16 + 2 * dcols.size() + ncols);
+  // and the wide head ladder's status words (HW_STAT_WORDS per dictionary column)
+  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16 + (2 + HW_STAT_WORDS) * dcols.size() + ncols);
   d_err = d_colroots + (size_t)ncols * 8;
   d_dstatus = d_err + 16;
   d_pwstat = d_dstatus + 2 * dcols.size();
+  d_hwstat = d_pwstat + ncols;
   T.pw_stat = d_pwstat;
   HIP_OR_THROW(hipMemset(d_err, 0, 64));
   HIP_OR_THROW(hipMemset(d_pwstat, 0, (size_t)ncols * 4));
@@ -771,8 +793,13 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     HIP_OR_THROW(hipMemset(d_dkeys, 0, cache_bytes));  // epoch 0 and seq 0 are never passed
     d_dlvl_seq = reinterpret_cast<uint64_t*>(d_dkeys + nd);
     d_dreuse = reinterpret_cast<uint32_t*>(d_dlvl_seq + DICT_LEVELS);
+    HIP_OR_THROW(hipMalloc((void**)&d_hw, (nd + 1) * sizeof(HeadWideDev)));
+    HIP_OR_THROW(hipMemset(d_hw, 0, (nd + 1) * sizeof(HeadWideDev)));  // epoch 0, build_seq 0: no ladder
+    hw_cols.assign(nd, HeadWideCol{});
+    hw_recs.assign(nd, HeadWideDev{});
     dict_cache_cols = nd;
   }
+  hw_stats.clear();
   {  // what dict_entry reads of the columns besides the plan: label block and table slot
     std::vector<uint8_t> shape(dcols.size() * (sizeof(ColTemplate) + sizeof(DictCol)));
     uint8_t* p = shape.data();
@@ -885,7 +912,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   PL.base = dalloc<uint32_t>(PL.total / 4 + 2);
   h_proof = halloc<uint8_t>(hdr_bytes + PL.total);
   memcpy(h_proof, pp.header.data(), hdr_bytes);
-  h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + 2 * (size_t)n_dict + (size_t)ncols);
+  h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + (2 + HW_STAT_WORDS) * (size_t)n_dict + (size_t)ncols);
   d_chal = dalloc<DevChal>(1);
   h_chal = halloc<DevChal>(1);
   d_dict_of = dalloc<uint32_t>((size_t)ncols);
@@ -1283,6 +1310,8 @@ struct ProveOptions {
   // forms that only 2^21 rows and more select; below 10 (unset: -1) = off
   long dict_plan_rows_log = -1;
   bool dict_cache_off = false;  // SEZKP_DICT_CACHE=0: every column rebuilt
+  bool head_wide = true;        // SEZKP_HEAD_WIDE=0: the head columns commit from 4-row groups only
+  uint64_t head_wide_cap = HEAD_WIDE_CAP_DEFAULT;  // SEZKP_HEAD_WIDE_CAP: L3 entries a head column may hold
   bool dist_intt = false;       // SEZKP_DIST_INTT=1: the distributed INTT (sharded, P > 1)
   // test hook: SEZKP_DEBUG_TRIP_GUARD=<rank> sets that rank's guard word, to
   // check that the failure is collective (tests/test_gpu_sharded.py; a good, a
@@ -1312,6 +1341,12 @@ struct ProveOptions {
     if (const char* pr = getenv("SEZKP_TEST_DICT_PLAN_ROWS_LOG")) o.dict_plan_rows_log = atol(pr);
     const char* dce = getenv("SEZKP_DICT_CACHE");
     o.dict_cache_off = dce && atoi(dce) == 0;
+    const char* hwe = getenv("SEZKP_HEAD_WIDE");
+    o.head_wide = !(hwe && hwe[0] == '0' && !hwe[1]);
+    if (const char* cap = getenv("SEZKP_HEAD_WIDE_CAP")) {
+      const long long v = atoll(cap);
+      if (v >= 1) o.head_wide_cap = std::min<uint64_t>((uint64_t)v, HEAD_WIDE_CAP_MAX);
+    }
     o.dist_intt = on("SEZKP_DIST_INTT");
     if (const char* trip = getenv("SEZKP_DEBUG_TRIP_GUARD")) {
       o.trip_guard = true;
@@ -1476,7 +1511,68 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     dict_dirty = true;  // until this proof completes
     dict_seq++;
   }
-  const DictCache dcache{d_dkeys, d_dreuse, d_dlvl_seq, d_dstatus, dict_epoch, dict_seq};
+  // ---- wide head ladders (prove_plan.h: head_wide_decide): which head
+  // columns read their ladder in this proof and which build it first, from
+  // what the last completed proof reported. A warm proof changes no record:
+  // no copy, no launch. SEZKP_HEAD_WIDE=0 (read per prove) leaves the state
+  // alone and commits from the 4-row groups.
+  const bool hw_on = opt.head_wide && n_dict > 0 && hw_cols.size() == (size_t)n_dict;
+  std::vector<uint64_t> hw_built((size_t)n_dict, 0);
+  uint64_t hw_max_entries = 0;
+  bool hw_build = false;
+  if (hw_on) {
+    std::vector<HeadWideDecision> dec((size_t)n_dict);
+    uint64_t slot = 0;
+    int nhead = 0;
+    for (int c = 0; c < n_dict; c++) {
+      if (dict_info[(size_t)c].kind != 6) continue;
+      nhead++;
+      dec[c] = head_wide_decide(hw_cols[c], dict_epoch, opt.head_wide_cap);
+      hw_build = hw_build || dec[c].build;
+      if (dec[c].use) slot = std::max(slot, dec[c].l3_entries + dec[c].low_entries);
+    }
+    slot = (slot + 4095) & ~(uint64_t)4095;
+    if (hw_build && slot > hwtabs_nodes) {
+      // a larger slot per head column: every ladder in place moves, so it is rebuilt
+      if (d_hwtabs) {
+        HIP_OR_THROW(hipStreamSynchronize(st));
+        (void)hipFree(d_hwtabs);
+        d_hwtabs = nullptr;
+        hwtabs_nodes = 0;
+      }
+      HIP_OR_THROW(hipMalloc((void**)&d_hwtabs, ((size_t)nhead * slot * 8 + 8) * sizeof(uint32_t)));
+      hwtabs_nodes = slot;
+      for (int c = 0; c < n_dict; c++) dec[c].build = dec[c].use;
+    }
+    bool changed = false;
+    int h = 0;
+    for (int c = 0; c < n_dict; c++) {
+      if (dict_info[(size_t)c].kind != 6) continue;
+      const HeadWideCol& hc = hw_cols[c];
+      HeadWideDev want = hw_recs[c];
+      if (!dec[c].use) {
+        want = HeadWideDev{};
+      } else if (dec[c].build) {
+        want = HeadWideDev{hc.olo, hc.dmin, hc.span, hc.dR, dict_epoch, dict_seq, (uint64_t)h * hwtabs_nodes,
+                           (uint64_t)h * hwtabs_nodes + dec[c].l3_entries};
+        hw_built[c] = dec[c].l3_entries + dec[c].low_entries;
+        hw_max_entries = std::max(hw_max_entries, dec[c].l3_entries);
+      }
+      if (memcmp(&want, &hw_recs[c], sizeof want) != 0) {
+        hw_recs[c] = want;
+        changed = true;
+      }
+      h++;
+    }
+    if (changed)
+      HIP_OR_THROW(hipMemcpyAsync(d_hw, hw_recs.data(), hw_recs.size() * sizeof(HeadWideDev), hipMemcpyHostToDevice, st));
+  }
+  DictCache dcache{d_dkeys, d_dreuse, d_dlvl_seq, d_dstatus, dict_epoch, dict_seq};
+  dcache.hwstat = d_hwstat;
+  if (hw_on && d_hwtabs) {
+    dcache.hw = d_hw;
+    dcache.hwtabs = d_hwtabs;
+  }
   // (One launch of a workgroup per column instead of the five flat launches,
   // chosen by the host when the last proof rebuilt nothing, was measured:
   // 5.3 against 24.6 us for a warm proof, but 138 against 38 us with the head
@@ -1568,6 +1664,8 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     HIP_OR_THROW(hipEventRecord(ev_cols, st2));
     // (the commit of the K <= 2 columns on a third stream beside table levels
     // 3..4 measured slower, round 6: profiles/r06/ab/dict_split_streams_ab.txt)
+    if (hw_build)
+      ok(launch_head_ladder(st, d_tmpl, d_dcols, n_dict, d_hw, dict_seq, d_hwtabs, hw_max_entries), "head_ladder");
     ok(launch_dict_commit(st, T, d_tmpl, d_dcols, n_dict, d_dpart, d_dplans, d_dtabs, d_outer, outer_stride, row_lo,
                           row_hi - row_lo, d_dlev, dcache, dict_tab_cap, dict_plan_rows),
        "col_commit_dict");
@@ -1598,9 +1696,12 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // (d_err = d_colroots + 8 ncols; sharded, every rank's word at d_err + 8),
     // and the dictionary cache's status words and the piecewise tables'
     // form words behind the 16 guard words
-    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots, (size_t)ncols * 32 + 4 * (16 + 2 * (size_t)n_dict + (size_t)ncols),
+    // and the wide head ladder's status words behind those
+    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots,
+                                (size_t)ncols * 32 + 4 * (16 + (2 + HW_STAT_WORDS) * (size_t)n_dict + (size_t)ncols),
                                 hipMemcpyDeviceToHost, st));
   };
+  std::vector<HeadWideObs> hw_obs((size_t)n_dict);
   auto host_1 = [&]() {
     const uint32_t* colroots_h = h_small;
     check_guards(h_small + 8 * ncols + gofs, nguard);
@@ -1612,6 +1713,18 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       const uint32_t units = h_small[8 * ncols + 16 + 2 * n_dict + c];
       st_pw_by_value += units != 0;
       st_pw_units += units;
+    }
+    for (int c = 0; c < n_dict; c++) {
+      const uint32_t* w = h_small + 8 * ncols + 16 + 2 * n_dict + ncols + HW_STAT_WORDS * c;
+      HeadWideObs& o = hw_obs[c];
+      o.lo = (int64_t)((uint64_t)w[0] | ((uint64_t)w[1] << 32));
+      o.hi = (int64_t)((uint64_t)w[2] | ((uint64_t)w[3] << 32));
+      o.mlo = (int32_t)w[4];
+      o.mhi = (int32_t)w[5];
+      o.delta = w[6];
+      o.wide = w[7];
+      o.fb_start = w[8];
+      o.fb_span = w[9];
     }
     std::vector<uint8_t> colroots((const uint8_t*)colroots_h, (const uint8_t*)colroots_h + (size_t)ncols * 32);
     for (int c = 0; c < ncols; c++) memcpy(h_proof + root_pos[c], colroots.data() + 32 * c, 32);
@@ -2068,6 +2181,27 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   dstat_entries = st_entries;
   pwstat_by_value = st_pw_by_value;
   pwstat_units = st_pw_units;
+  // the wide head ladders: what this proof saw feeds the next proof's decision
+  hw_stats.clear();
+  for (int c = 0; c < n_dict && hw_cols.size() == (size_t)n_dict; c++) {
+    if (dict_info[(size_t)c].kind != 6) continue;
+    head_wide_observe(hw_cols[c], dict_epoch, hw_obs[c]);
+    const HeadWideDev& r = hw_recs[c];
+    const bool in_place = r.epoch == dict_epoch && r.span != 0;
+    sezkp_head_wide_info s{};
+    s.col = dict_info[(size_t)c].col;
+    s.tape = dict_info[(size_t)c].tape;
+    s.origin = in_place ? r.olo : 0;
+    s.span = in_place ? r.span : 0;
+    s.dR = in_place ? r.dR : 0;
+    s.R = hw_obs[c].hi >= hw_obs[c].lo ? (uint64_t)(hw_obs[c].hi - hw_obs[c].lo) + 1 : 0;
+    s.entries_built = hw_built[c];
+    s.groups_wide = hw_obs[c].wide;
+    s.groups_fallback = (uint64_t)hw_obs[c].fb_start + hw_obs[c].fb_span;
+    s.groups_out_of_span = hw_obs[c].fb_span;
+    s.table_bytes = in_place ? hwtabs_nodes * 32 : 0;
+    hw_stats.push_back(s);
+  }
   return out;
 }
 
@@ -2407,6 +2541,15 @@ int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* cctx, uint32_t* cols_rebuilt
   *cols_reused = have ? ctx->dstat_reused : 0;
   *entries_rebuilt = have ? ctx->dstat_entries : 0;
   return SEZKP_OK;
+}
+int32_t sezkp_ctx_head_wide_stats(const sezkp_ctx* cctx, sezkp_head_wide_info* out, int32_t max) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || (max > 0 && !out) || max < 0) return SEZKP_E_INVALID;
+  if (ctx->busy()) return SEZKP_E_INVALID;  // the records are rewritten by the proof in flight
+  if (!ctx->loaded || !ctx->have_plans) return 0;
+  const int32_t cnt = std::min<int32_t>(max, (int32_t)ctx->hw_stats.size());
+  for (int32_t i = 0; i < cnt; i++) out[i] = ctx->hw_stats[(size_t)i];
+  return cnt;
 }
 int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* cctx, uint32_t* cols_by_value, uint32_t* cols_by_block,
                                  uint64_t* units_built) {

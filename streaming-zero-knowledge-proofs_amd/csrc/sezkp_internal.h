@@ -229,6 +229,7 @@ struct DictKey {
   int64_t lo, hi, mlo, mhi;
   uint64_t epoch;
 };
+struct HeadWideDev;
 struct DictCache {
   DictKey* keys;      // per column
   uint32_t* reuse;    // per column: 1 = the tables in place are this proof's
@@ -236,12 +237,42 @@ struct DictCache {
   uint32_t* status;   // per column (rebuilt, entries rebuilt): goes home with the column roots
   uint64_t epoch;
   uint64_t seq;       // this proof's number on the context (never 0)
+  // the wide head ladder (HeadWideDev below): the status words (HW_STAT_WORDS
+  // per column, home with the column roots), and per column the record and
+  // the buffer of the ladders (hw null: the commit does not take them)
+  uint32_t* hwstat = nullptr;
+  const HeadWideDev* hw = nullptr;
+  const uint32_t* hwtabs = nullptr;
 };
 // Head delta plan: inside a block head[r] = head[r-1] + mv[r], so an aligned
 // 4-row head group is a function of (head[g], mv[g+1], mv[g+2], mv[g+3]):
 // TD[c0 + R (d1 + dR d2 + dR^2 d3)] = H(T_1[c0 + R c1], T_1[c2 + R c3]) with
 // c_j = c_{j-1} + mv_j (codes). Groups with a block start at g+1..g+3 use
 // the two T_1 nodes directly. Needs R^2 <= DICT_CAP and R dR^3 <= DICT_CAP.
+// Wide head ladder: inside a block an aligned 8-row head group is a function
+// of (head[g], mv[g+1..g+7]). A head column with a delta plan keeps, across
+// the proofs of an epoch, a value-keyed table of those groups over the heads
+// [olo, olo + span) and the moves [dmin, dmin + dR):
+//   L0[h] labelled leaf, L1[h, m1] = H(L0[h], L0[h + m1]),
+//   L2[h, m1..m3] = H(L1[h, m1], L1[h + m1 + m2, m3]),
+//   L3[h, m1..m7] = H(L2[h; m1..m3], L2[h + m1 + .. + m4; m5..m7]),
+// L3 at (h - olo) + span sum_i (m_i - dmin) dR^(i-1), never at the proof's own
+// minimum. L0..L2 cover the heads a group can reach from the span (7 moves)
+// and are read by the build only. The host decides when to build
+// (prove_plan.h: head_wide_decide) and writes this record then; the commit
+// takes the ladder when `epoch` is the proof's dictionary epoch, and any
+// group it does not cover (a block start in rows 1..7, a first head outside
+// the span, moves outside the ladder's) through the 4-row delta nodes.
+struct HeadWideDev {
+  int64_t olo, dmin;
+  uint32_t span, dR;
+  uint64_t epoch;      // dictionary epoch the ladder was built in
+  uint64_t build_seq;  // number of the proof that builds it (k_head_ladder)
+  uint64_t l3, low;    // node offsets of L3 and of L0 | L1 | L2 in the ladder buffer
+};
+// builds the ladders whose build_seq is `seq`: four launches (levels 0..3)
+hipError_t launch_head_ladder(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
+                              const HeadWideDev* d_hw, uint64_t seq, uint32_t* d_hwtabs, uint64_t max_entries);
 __host__ __device__ inline int dlev_base(int level) { return level == 6 ? 0 : level == 7 ? 16 : level == 8 ? 24 : 28; }
 // extra lane rows (log2) of the dictionary commitment for table level K:
 // high K leaves few table nodes per 64 rows, so lanes take 2^(6+a) rows

@@ -1221,6 +1221,46 @@ struct DeltaNodes {
     }
   }
 };
+// head delta plan with the wide ladder (HeadWideDev): node j = the 8-row
+// group at row 8j of the lane, one L3 node; a group the ladder does not cover
+// is the parent of its two DeltaNodes nodes, so the lane's root never depends
+// on the ladder's coverage. cnt: this lane's groups, 10 bits each: from L3,
+// fallen back for a block start in rows 1..7, fallen back for a first head
+// outside the span (span = 0: the proof's moves are not all the ladder's)
+struct WideNodes {
+  DeltaNodes dn;
+  const uint32_t* l3;
+  int64_t olo;
+  int32_t wdmin;
+  uint32_t span, wdR;
+  mutable uint32_t cnt;
+  struct Raw {
+    uint64_t f, m;
+    int64_t h0;
+  };
+  __device__ __forceinline__ Raw raw(int j) const {
+    const uint64_t g = (uint64_t)j << 3;
+    return Raw{*reinterpret_cast<const uint64_t*>(dn.fp + g), *reinterpret_cast<const uint64_t*>(dn.mp + g),
+               dn.hp[g]};
+  }
+  __device__ __forceinline__ void node(const Raw& r, int j, uint32_t (&h)[8]) const {
+    const uint64_t c0 = (uint64_t)(r.h0 - olo);
+    const bool starts = (r.f & 0x0101010101010100ull) != 0;
+    if (!starts && c0 < span) {
+      uint32_t idx = 0;
+#pragma unroll
+      for (int i = 7; i >= 1; i--) idx = idx * wdR + (uint32_t)((int32_t)(int8_t)(r.m >> (8 * i)) - wdmin);
+      node_load(l3 + 8 * (uint64_t)((uint32_t)c0 + span * idx), h);  // < span dR^7 <= 2^24
+      cnt += 1u;
+    } else {
+      uint32_t a[8], b[8];
+      dn.get(2 * j, a);
+      dn.get(2 * j + 1, b);
+      b3_parent(a, b, h);
+      cnt += starts ? 1u << 10 : 1u << 20;
+    }
+  }
+};
 template <typename Key>
 struct RawLeaves {
   const Key* p;
@@ -1726,6 +1766,13 @@ __global__ void __launch_bounds__(TR_THREADS) k_dict_plan(const int64_t* __restr
     dc.reuse[blockIdx.x] = same ? 1u : 0u;
     dc.status[2 * blockIdx.x] = same ? 0u : 1u;
     dc.status[2 * blockIdx.x + 1] = entries;
+    // the host's inputs for the wide head ladder, and the commit's group counters zeroed
+    uint32_t* hs = dc.hwstat + HW_STAT_WORDS * blockIdx.x;
+    hs[0] = (uint32_t)(uint64_t)lo; hs[1] = (uint32_t)((uint64_t)lo >> 32);
+    hs[2] = (uint32_t)(uint64_t)hi; hs[3] = (uint32_t)((uint64_t)hi >> 32);
+    hs[4] = (uint32_t)(int32_t)mlo; hs[5] = (uint32_t)(int32_t)mhi;
+    hs[6] = P.delta;
+    hs[7] = hs[8] = hs[9] = 0;
   }
 }
 
@@ -1857,7 +1904,10 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
                                                                    const uint32_t* __restrict__ tabs,
                                                                    uint32_t* __restrict__ outer, uint64_t outer_stride,
                                                                    uint64_t row0, uint64_t row_end,
-                                                                   uint32_t* __restrict__ dlev) {
+                                                                   uint32_t* __restrict__ dlev,
+                                                                   const HeadWideDev* __restrict__ hw,
+                                                                   const uint32_t* __restrict__ hwtabs,
+                                                                   uint64_t epoch, uint32_t* __restrict__ hwstat) {
   __shared__ uint32_t lds[2][8][DICT_WG_LANES];
   // (XCD-interleaved column orders, so that one XCD's workgroups gather
   // from one column's tables at a time, measured slower in rounds 1 and 3)
@@ -1876,6 +1926,14 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
   const uint64_t lrow = wg_row + ((uint64_t)lane << llog);
   const uint64_t nch_all = T.n >> COL_CHUNK_LOG2;
   uint32_t* dl = dlev + 8 * (uint64_t)by * nch_all * DLEV_NODES;
+  // the wide head ladder of this column, if it is this epoch's (uniform per workgroup)
+  bool wide = false;
+  uint32_t wcnt = 0;
+  HeadWideDev W{};
+  if (hw && ct.kind == 6 && P.delta) {
+    W = hw[by];
+    wide = W.epoch == epoch && W.span != 0;
+  }
   if (lrow < row_end) {
     uint32_t h[8];
     switch (ct.kind) {
@@ -1887,7 +1945,13 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
           const uint64_t o = (uint64_t)ct.tape * T.n + lrow;
           const DeltaNodes dn{T.head + o, T.mv + o, T.row_flags + lrow, tab + 8 * (uint64_t)DICT_CAP,
                               tab + 16 * (uint64_t)DICT_CAP, P.min, P.dmin, P.R, P.dR};
-          if (a == 1) lane_tree_pf<5>(dn, h);  // 4-row groups: 2^(4 + a) per lane
+          if (wide) {  // 8-row groups: 2^(3 + a) per lane
+            const bool moves_in = P.dmin >= W.dmin && P.dmin + (int64_t)P.dR <= W.dmin + (int64_t)W.dR;
+            const WideNodes wn{dn, hwtabs + 8 * W.l3, W.olo, (int32_t)W.dmin, moves_in ? W.span : 0u, W.dR, 0u};
+            if (a == 1) lane_tree_pf<4>(wn, h);
+            else lane_tree_pf<3>(wn, h);
+            wcnt = wn.cnt;
+          } else if (a == 1) lane_tree_pf<5>(dn, h);  // 4-row groups: 2^(4 + a) per lane
           else lane_tree_pf<4>(dn, h);
         } else {
           dict_lane<int32_t>(dict_keys<int32_t>(T, ct) + lrow, P, tab, ctp, h);
@@ -1900,6 +1964,20 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
     node_store(dl + 8 * ((lrow >> COL_CHUNK_LOG2) * DLEV_NODES + dlev_base(llog) +
                          ((lrow >> llog) & ((1u << (COL_CHUNK_LOG2 - llog)) - 1))),
                h);
+  }
+  if (wide) {  // the wave's group counts: one atomic per non-zero counter
+    uint32_t p = (wcnt & 0x3ffu) | (((wcnt >> 10) & 0x3ffu) << 16), q = wcnt >> 20;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+      p += __shfl_xor(p, o, 64);
+      q += __shfl_xor(q, o, 64);
+    }
+    if ((lane & 63) == 0) {
+      uint32_t* hs = hwstat + HW_STAT_WORDS * by;
+      if (p & 0xffffu) atomicAdd(hs + 7, p & 0xffffu);
+      if (p >> 16) atomicAdd(hs + 8, p >> 16);
+      if (q) atomicAdd(hs + 9, q);
+    }
   }
   __syncthreads();
   int cnt = DICT_WG_LANES, cur = 0;
@@ -1935,7 +2013,80 @@ __global__ void __launch_bounds__(DICT_WG_LANES) k_col_commit_dict(TraceDev T, c
   }
 }
 
+// Level LVL of the wide head ladders (HeadWideDev) that proof `seq` builds:
+// grid (entries, dictionary columns), grid-stride over the level's entries.
+// An entry of L1 / L2 whose heads leave the widened range [wlo, wlo + sw) is
+// never read (no group that starts in the span reaches it) and is skipped.
+template <int LVL>
+__global__ void __launch_bounds__(TR_THREADS) k_head_ladder(const ColTemplate* __restrict__ tmpl,
+                                                            const DictCol* __restrict__ dcols,
+                                                            const HeadWideDev* __restrict__ hw, uint64_t seq,
+                                                            uint32_t* __restrict__ tabs) {
+  const HeadWideDev W = hw[blockIdx.y];
+  if (W.build_seq != seq) return;
+  constexpr int NM = (1 << LVL) - 1;             // moves of an entry
+  constexpr int HALF = LVL > 0 ? 1 << (LVL - 1) : 0;  // rows of a child
+  const uint32_t dR = W.dR;
+  const int64_t dmax = W.dmin + (int64_t)dR - 1;
+  const int64_t neg = W.dmin < 0 ? W.dmin : 0, pos = dmax > 0 ? dmax : 0;
+  const int64_t wlo = W.olo + 7 * neg;
+  const uint32_t sw = W.span + 7u * (uint32_t)(pos - neg);
+  const uint32_t d3 = dR * dR * dR;
+  uint32_t* l0 = tabs + 8 * W.low;
+  uint32_t* l1 = l0 + 8 * (uint64_t)sw;
+  uint32_t* l2 = l1 + 8 * (uint64_t)sw * dR;
+  uint32_t* l3 = tabs + 8 * W.l3;
+  const uint32_t s = LVL == 3 ? W.span : sw;  // first heads of the level
+  const uint32_t cnt = LVL == 0 ? sw : LVL == 1 ? sw * dR : LVL == 2 ? sw * d3 : W.span * d3 * d3 * dR;
+  const uint32_t base = LVL == 3 ? (uint32_t)(W.olo - wlo) : 0u;  // code (head - wlo) of the first one
+  const ColTemplate ct = tmpl[dcols[blockIdx.y].col];
+  for (uint32_t e = blockIdx.x * TR_THREADS + threadIdx.x; e < cnt; e += gridDim.x * TR_THREADS) {
+    uint32_t h[8];
+    if constexpr (LVL == 0) {
+      leaf_labeled_rt(ct, gl_from_i64(wlo + (int64_t)e), h);
+      node_store(l0 + 8 * (uint64_t)e, h);
+    } else {
+      const uint32_t c = base + e % s;
+      uint32_t rest = e / s;
+      int64_t run = c, cr = 0;
+      uint32_t li = 0, ri = 0, lm = 1, rm = 1;
+      bool ok = true;
+#pragma unroll
+      for (int i = 1; i <= NM; i++) {
+        const uint32_t d = rest % dR;
+        rest /= dR;
+        run += W.dmin + (int64_t)d;
+        ok = ok && run >= 0 && run < (int64_t)sw;
+        if (i < HALF) { li += d * lm; lm *= dR; }
+        else if (i == HALF) cr = run;
+        else { ri += d * rm; rm *= dR; }
+      }
+      if (!ok) continue;
+      const uint32_t* ch = LVL == 1 ? l0 : LVL == 2 ? l1 : l2;
+      uint32_t* dst = LVL == 1 ? l1 : LVL == 2 ? l2 : l3;
+      uint32_t a[8], b[8];
+      node_load(ch + 8 * (uint64_t)(c + sw * li), a);
+      node_load(ch + 8 * (uint64_t)((uint32_t)cr + sw * ri), b);
+      b3_parent(a, b, h);
+      node_store(dst + 8 * (uint64_t)e, h);
+    }
+  }
+}
+
 // ------------------------------------------------------------------ host
+hipError_t launch_head_ladder(hipStream_t st, const ColTemplate* d_tmpl, const DictCol* d_dcols, int ndict,
+                              const HeadWideDev* d_hw, uint64_t seq, uint32_t* d_hwtabs, uint64_t max_entries) {
+  if (ndict == 0 || max_entries == 0) return hipSuccess;
+  if (max_entries > (1ull << 24)) return hipErrorInvalidValue;
+  // the lower levels are small: the grid of L3 would only read the record
+  const unsigned g3 = (unsigned)std::min<uint64_t>((max_entries + TR_THREADS - 1) / TR_THREADS, 2048);
+  const unsigned glow = std::min(g3, 64u);
+  hipLaunchKernelGGL(k_head_ladder<0>, dim3(glow, ndict), dim3(TR_THREADS), 0, st, d_tmpl, d_dcols, d_hw, seq, d_hwtabs);
+  hipLaunchKernelGGL(k_head_ladder<1>, dim3(glow, ndict), dim3(TR_THREADS), 0, st, d_tmpl, d_dcols, d_hw, seq, d_hwtabs);
+  hipLaunchKernelGGL(k_head_ladder<2>, dim3(glow, ndict), dim3(TR_THREADS), 0, st, d_tmpl, d_dcols, d_hw, seq, d_hwtabs);
+  hipLaunchKernelGGL(k_head_ladder<3>, dim3(g3, ndict), dim3(TR_THREADS), 0, st, d_tmpl, d_dcols, d_hw, seq, d_hwtabs);
+  return hipGetLastError();
+}
 hipError_t launch_trace_image(hipStream_t st, const int8_t* raw_mv, const uint8_t* raw_hw, const uint16_t* raw_ws,
                               uint64_t n, int tau, int8_t* mv, uint8_t* wf, uint16_t* ws, uint64_t r0, uint64_t r1) {
   if (r1 > n) r1 = n;
@@ -1988,6 +2139,7 @@ hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTempla
   hipError_t e = dict_shape_ok(T, row0, nrows);
   if (e != hipSuccess) return e;
   if (tab_cap == 0 || tab_cap > DICT_CAP) return hipErrorInvalidValue;
+  if (!dc.hwstat || (dc.hw && !dc.hwtabs)) return hipErrorInvalidValue;
   // parts of 1..8 sweeps: ~64 per column (the partial buffer holds n / 4096)
   const int sweeps = (int)std::max<uint64_t>(1, std::min<uint64_t>(8, nrows / (64ull * DICT_RANGE_STEP)));
   const uint64_t prow = (uint64_t)sweeps * DICT_RANGE_STEP;
@@ -2011,7 +2163,7 @@ hipError_t launch_dict_commit(hipStream_t st, const TraceDev& T, const ColTempla
   const uint64_t wg_rows = (uint64_t)DICT_WG_LANES << DICT_LANE_LOG;  // rows of a WG at a = 0
   const unsigned gx = (unsigned)((nrows + wg_rows - 1) / wg_rows);
   hipLaunchKernelGGL(k_col_commit_dict, dim3(gx, ndict), dim3(DICT_WG_LANES), 0, st, T, d_tmpl, d_dcols, d_plans, d_dtabs,
-                     outer_nodes, outer_stride_nodes, row0, row0 + nrows, d_dlev);
+                     outer_nodes, outer_stride_nodes, row0, row0 + nrows, d_dlev, dc.hw, dc.hwtabs, dc.epoch, dc.hwstat);
   return hipGetLastError();
 }
 

@@ -38,6 +38,7 @@ EXPORTS = [
     "sezkp_ctx_create_sharded_solo", "sezkp_blocks_decode_jsonl_lines", "sezkp_ctx_dict_plans",
     "sezkp_ctx_air_audit", "sezkp_stark_v1_air_audit", "sezkp_ctx_dict_cache_stats", "sezkp_ctx_pw_table_stats",
     "sezkp_ctx_verify_batch", "sezkp_stark_v1_verify_batch", "sezkp_ctx_verify_times",
+    "sezkp_ctx_head_wide_stats",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -76,6 +77,12 @@ class DictPlanInfo(C.Structure):
     _fields_ = [("col", C.c_uint32), ("kind", C.c_uint32), ("tape", C.c_uint32), ("K", C.c_int32),
                 ("a", C.c_uint32), ("delta", C.c_uint32), ("R", C.c_uint32), ("dR", C.c_uint32),
                 ("min", C.c_int64)]
+
+
+class HeadWideInfo(C.Structure):  # sezkp_head_wide_info
+    _fields_ = [("col", C.c_uint32), ("tape", C.c_uint32), ("origin", C.c_int64), ("span", C.c_uint32),
+                ("dR", C.c_uint32), ("R", C.c_uint64), ("entries_built", C.c_uint64), ("groups_wide", C.c_uint64),
+                ("groups_fallback", C.c_uint64), ("groups_out_of_span", C.c_uint64), ("table_bytes", C.c_uint64)]
 
 
 class SezkpError(RuntimeError):
@@ -157,6 +164,7 @@ def _load():
                                              C.POINTER(C.c_uint64)]
     L.sezkp_ctx_pw_table_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_uint64)]
+    L.sezkp_ctx_head_wide_stats.argtypes = [C.c_void_p, C.POINTER(HeadWideInfo), C.c_int32]
     L.sezkp_gl_ntt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
     L.sezkp_gl_coset_lde_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]

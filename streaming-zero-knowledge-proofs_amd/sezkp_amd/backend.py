@@ -377,6 +377,19 @@ class ProverContext:
             raise SezkpError(rc, "dict_cache_stats: a proof is in flight on this context (or the context is closed)")
         return {"cols_rebuilt": rebuilt.value, "cols_reused": reused.value, "entries_rebuilt": entries.value}
 
+    def head_wide_stats(self) -> list:
+        """The wide head ladder in the last completed prove, one dict per head
+        dictionary column: {col, tape, origin, span, dR, R, entries_built,
+        groups_wide, groups_fallback, groups_out_of_span, table_bytes}
+        (sezkp_ctx_head_wide_stats; empty before the first prove of an upload)."""
+        from ._lib import HeadWideInfo
+        cap = max(1, self.tau)
+        buf = (HeadWideInfo * cap)()
+        n = lib.sezkp_ctx_head_wide_stats(self._h, buf, cap)
+        if n < 0:
+            raise SezkpError(n, "head_wide_stats: a proof is in flight on this context (or the context is closed)")
+        return [{f: int(getattr(buf[i], f)) for f, _ in HeadWideInfo._fields_} for i in range(n)]
+
     def pw_table_stats(self) -> dict:
         """The per-block piecewise columns' table form in the last completed
         prove: {cols_by_value, cols_by_block, units_built}
