@@ -267,6 +267,82 @@ int32_t sezkp_ctx_head_wide_stats(const sezkp_ctx* ctx, sezkp_head_wide_info* ou
 int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* ctx, uint32_t* cols_by_value, uint32_t* cols_by_block,
                                  uint64_t* units_built);
 
+/* ------------------------------------------------ proving from a raw trace
+ * Every entry point above starts from BlockSummary data: the caller has run
+ * partition_trace and hashed the manifest on the host. These start from the
+ * movement log itself, TraceFile (crates/sezkp-trace/src/format.rs:59-68), and
+ * run partition_trace (partition.rs:43-150) and the manifest commitment
+ * (sezkp-merkle lib.rs:85-157) on the device: the block shape is uniform,
+ * block k covers rows [k b, min((k + 1) b, t)). Step-major arrays as in
+ * sezkp_block_view; moves are any i8. The arrays may be host memory or device
+ * memory of the context's device (hipPointerGetAttributes decides): a trace
+ * produced on the GPU is uploaded without a trip through the host. */
+typedef struct sezkp_trace_view {
+  uint64_t t;                 /* steps */
+  uint32_t tau;               /* work tapes (<= 255: TraceFile::tau is a u8) */
+  uint32_t b;                 /* steps per block (>= 1) */
+  const int8_t* input_mv;     /* [t] */
+  const int8_t* mv;           /* [t*tau] */
+  const uint8_t* has_write;   /* [t*tau] */
+  const uint16_t* wsym;       /* [t*tau] (symbol when has_write) */
+} sezkp_trace_view;
+/* prove / prove_borrow / prove_async: manifest_root may be NULL; the proof
+ * absorbs the manifest root of the trace image it reads (commit_blocks of its
+ * partition, lib.rs:214-222), which the device computes and sends home with
+ * the column roots: no copy and no synchronisation of its own. SEZKP_E_INVALID
+ * "manifest root from the trace: the active trace image was uploaded as
+ * blocks" when the image did not come from sezkp_ctx_upload_trace /
+ * sezkp_ctx_stage_trace. Without the flag nothing changes: a NULL root is a
+ * null argument, a given root is used as given, also on a trace image. */
+#define SEZKP_FLAG_ROOT_FROM_TRACE 2u
+/* sezkp_ctx_upload for a trace: partition_trace(trace, b) on the device
+ * (partition.rs:43-150), planned exactly as the upload of those blocks (same
+ * workspace, same errors: "n_base must be a power of two (got 3000)"). A null
+ * view or array, b = 0, tau > 255, more than 2^32 - 1 blocks and the shape
+ * errors are answered before any device call. A block whose head leaves the
+ * i32 range fails with the message of prove and leaves the context usable
+ * (without a trace). Sharded contexts: SEZKP_E_INVALID. */
+int32_t sezkp_ctx_upload_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len);
+/* sezkp_ctx_stage for a trace of the uploaded shape (tau, block count and
+ * block boundaries; the image in place may have come as blocks or as a trace,
+ * and a block view may be staged on a trace context). Only the copies of the
+ * four step arrays go on the copy stream; the proof that takes the image
+ * partitions it, once, on its own streams. Lifetime of the arrays: as for
+ * sezkp_ctx_stage. */
+int32_t sezkp_ctx_stage_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len);
+/* Reports on the trace image the proofs read. All three: SEZKP_E_INVALID while
+ * a proof is in flight, with a staged trace no prove has consumed, or when
+ * the image was uploaded as blocks.
+ * The manifest root: commit_blocks (lib.rs:214-222, the batch merkle_root), or
+ * with frontier != 0 the Frontier root (lib.rs:167-208) that .jsonl block
+ * files are committed with, computed on the host from the leaves. */
+int32_t sezkp_ctx_manifest_root(sezkp_ctx* ctx, int32_t frontier, uint8_t out[32], char* err, size_t err_len);
+/* leaf_hash of every block (lib.rs:85-117), 32 bytes each, at most max_leaves
+ * (SEZKP_E_INVALID when the trace has more blocks). */
+int32_t sezkp_ctx_manifest_leaves(sezkp_ctx* ctx, uint8_t* out32, uint64_t max_leaves, char* err, size_t err_len);
+/* The Vec<BlockSummary> partition_trace returns (partition.rs:43-150), with
+ * the windows, head offsets and input-head positions the device computed. The
+ * step arrays are copied from `steps` when given (same t and tau), else read
+ * back from the device. Free with sezkp_blocks_free. */
+struct sezkp_blocks;
+int32_t sezkp_ctx_trace_blocks(sezkp_ctx* ctx, const sezkp_trace_view* steps, struct sezkp_blocks** out, char* err,
+                               size_t err_len);
+/* Stateless, device 0: partition_trace + commit_blocks + StarkV1::prove
+ * (lib.rs:129-141) in one upload and one proof. manifest_root_out (may be
+ * NULL) receives the root the proof absorbed. Argument and shape errors are
+ * answered before any device is touched. */
+int32_t sezkp_stark_v1_prove_trace(const sezkp_trace_view* trace, uint32_t flags, sezkp_buf* proof_bytes,
+                                   uint8_t manifest_root_out[32], char* err, size_t err_len);
+/* TraceFile as CBOR (sezkp-trace io.rs, ciborium; what a VM front end or
+ * generate_trace writes): decode into a handle that owns the arrays its view
+ * points to (b = 0: the caller sets it on a copy of the view), and encode
+ * (version 1, meta null) byte for byte as the reference writes it. */
+typedef struct sezkp_trace sezkp_trace;
+int32_t sezkp_trace_decode_cbor(const uint8_t* data, size_t len, sezkp_trace** out, char* err, size_t err_len);
+int32_t sezkp_trace_encode_cbor(const sezkp_trace_view* trace, sezkp_buf* out);
+const sezkp_trace_view* sezkp_trace_view_of(const sezkp_trace* t);
+void sezkp_trace_free(sezkp_trace* t);
+
 /* ------------------------------------------------ full-trace AIR audit
  * Does the committed trace satisfy the AIR, on every row? The reference
  * verifier recomputes the composition (air.rs:49-136) only on its 30 opened

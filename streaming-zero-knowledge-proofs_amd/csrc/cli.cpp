@@ -1,5 +1,8 @@
 // cli.cpp — `sezkp-cli` drop-in for the STARK path on MI355X:
 //   prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]
+//   prove  --backend stark --trace T.cbor --b STEPS_PER_BLOCK --out P [--out-blocks F] [--out-manifest F]
+//          [--manifest M] [--stream]
+//          (from the movement log: partition and manifest on the device; --manifest is compared with its root)
 //   verify --backend stark --blocks B --manifest M --proof P [--assume-committed] [--gpu]
 //          (--gpu: the Merkle paths are hashed on device 0, sezkp_stark_v1_verify_batch; same output)
 //   commit --blocks B(.cbor|.json|.jsonl|.ndjson) --out M
@@ -101,8 +104,8 @@ std::string pretty_artifact(const Artifact& a) {
 }
 
 struct Args {
-  std::string cmd, backend = "stark", blocks, manifest, out, proof, input;
-  bool stream = false, assume = false, json = false, gpu = false;
+  std::string cmd, backend = "stark", blocks, manifest, out, proof, input, trace, out_blocks, out_manifest;
+  bool stream = false, assume = false, json = false, gpu = false, b_given = false;
   std::string t = "32", b = "4", tau = "2";  // simulate defaults (main.rs:87-100)
 };
 
@@ -165,7 +168,106 @@ int load_inputs(const Args& a, BlockStore& bs, uint8_t mroot[32]) {
   return 0;
 }
 
+void usage();
+int write_artifact(const Args& a, const std::vector<uint8_t>& cbor, uint32_t tau);
+std::vector<uint8_t> manifest_json(const uint8_t root[32], uint32_t n_leaves);
+
+// `prove --trace`: the movement log (TraceFile CBOR) instead of blocks and a
+// manifest. The device partitions it into blocks of --b steps and commits the
+// manifest (sezkp_ctx_upload_trace); --manifest, when given, must carry that
+// root; --out-blocks / --out-manifest write what `simulate` and `commit` would
+// have written for the same trace.
+int cmd_prove_trace(const Args& a) {
+  if (!a.blocks.empty()) { fprintf(stderr, "Error: --blocks and --trace are mutually exclusive\n"); usage(); return 2; }
+  if (ext_lower(a.trace) != "cbor") { fprintf(stderr, "Error: --trace reads a .cbor trace file\n"); usage(); return 2; }
+  if (!a.b_given || a.out.empty()) { fprintf(stderr, "Error: prove --trace needs --b and --out\n"); usage(); return 2; }
+  const unsigned long long b = strtoull(a.b.c_str(), nullptr, 10);
+  if (b == 0 || b > 0xFFFFFFFFull) { fprintf(stderr, "Error: --b must be in 1..=2^32-1\n"); return 2; }
+  if (!a.out_blocks.empty()) {
+    const std::string e = ext_lower(a.out_blocks);
+    if (e != "cbor" && e != "jsonl" && e != "ndjson") {
+      fprintf(stderr, "Error: --out-blocks must end in .cbor, .jsonl or .ndjson\n");
+      return 2;
+    }
+  }
+  std::string err;
+  std::vector<uint8_t> raw;
+  if (!read_file(a.trace, raw, err)) { fprintf(stderr, "Error: reading trace: %s\n", err.c_str()); return 1; }
+  char msg[512] = {0};
+  sezkp_trace* th = nullptr;
+  if (sezkp_trace_decode_cbor(raw.data(), raw.size(), &th, msg, sizeof msg)) {
+    fprintf(stderr, "Error: reading trace: %s\n", msg);
+    return 1;
+  }
+  sezkp_trace_view tv = *sezkp_trace_view_of(th);
+  tv.b = (uint32_t)b;
+  uint8_t want[32], root[32];
+  const bool have_manifest = !a.manifest.empty();
+  int rc = 1;
+  sezkp_ctx* ctx = nullptr;
+  sezkp_buf pb{};
+  do {
+    if (have_manifest && !load_manifest(a.manifest, want, nullptr, err)) {
+      fprintf(stderr, "Error: reading manifest: %s\n", err.c_str());
+      break;
+    }
+    ctx = sezkp_ctx_create(0, msg, sizeof msg);
+    if (!ctx) { fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg); break; }
+    if (sezkp_ctx_upload_trace(ctx, &tv, msg, sizeof msg) || sezkp_ctx_manifest_root(ctx, 0, root, msg, sizeof msg)) {
+      fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg);
+      break;
+    }
+    if (have_manifest && memcmp(want, root, 32) != 0) {
+      fprintf(stderr, "Error: stark-v1 proof failed: manifest root mismatch: manifest=%s, trace=%s\n",
+              hex(want, 32).c_str(), hex(root, 32).c_str());
+      break;
+    }
+    const uint32_t flags = SEZKP_FLAG_ROOT_FROM_TRACE | (a.stream ? SEZKP_FLAG_STREAMING : 0);
+    if (sezkp_ctx_prove(ctx, nullptr, flags, &pb, msg, sizeof msg)) {
+      fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg);
+      break;
+    }
+    const uint32_t nblk = (uint32_t)((tv.t + b - 1) / b);
+    if (!a.out_blocks.empty()) {
+      sezkp_blocks* bh = nullptr;
+      if (sezkp_ctx_trace_blocks(ctx, &tv, &bh, msg, sizeof msg)) { fprintf(stderr, "Error: %s\n", msg); break; }
+      sezkp_buf buf{};
+      const int32_t erc = ext_lower(a.out_blocks) == "cbor" ? sezkp_blocks_encode_cbor(sezkp_blocks_view(bh), &buf)
+                                                            : sezkp_blocks_encode_jsonl(sezkp_blocks_view(bh), &buf);
+      sezkp_blocks_free(bh);
+      if (erc != SEZKP_OK) { fprintf(stderr, "Error: encoding blocks failed (%d)\n", erc); break; }
+      std::vector<uint8_t> out(buf.data, buf.data + buf.len);
+      sezkp_buf_free(&buf);
+      if (!write_file(a.out_blocks, out, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); break; }
+    }
+    if (!a.out_manifest.empty()) {
+      // the root `commit` gives for the blocks file: the Frontier for JSON Lines
+      uint8_t mroot[32];
+      memcpy(mroot, root, 32);
+      if (is_jsonl_like(a.out_blocks) && sezkp_ctx_manifest_root(ctx, 1, mroot, msg, sizeof msg)) {
+        fprintf(stderr, "Error: %s\n", msg);
+        break;
+      }
+      const std::vector<uint8_t> out =
+          ext_lower(a.out_manifest) == "cbor" ? encode_manifest_cbor(mroot, nblk) : manifest_json(mroot, nblk);
+      if (!write_file(a.out_manifest, out, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); break; }
+    }
+    std::vector<uint8_t> proof(pb.data, pb.data + pb.len);
+    uint64_t domain_n = 0;
+    for (int i = 7; i >= 0; i--) domain_n = (domain_n << 8) | proof[i];
+    std::vector<MetaEntry> meta = {{"proto", true, "stark-v1", 0}, {"domain_n", false, "", domain_n},
+                                   {"tau", false, "", tv.tau}};
+    if (a.stream) meta.push_back({"mode", true, "streaming", 0});
+    rc = write_artifact(a, encode_artifact_cbor("stark", root, proof, meta), tv.tau);
+  } while (false);
+  sezkp_buf_free(&pb);
+  if (ctx) sezkp_ctx_destroy(ctx);
+  sezkp_trace_free(th);
+  return rc;
+}
+
 int cmd_prove(const Args& a) {
+  if (!a.trace.empty()) return cmd_prove_trace(a);
   std::string err;
   BlockStore bs;
   uint8_t mroot[32];
@@ -177,6 +279,12 @@ int cmd_prove(const Args& a) {
   if (rc) { fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg); return 1; }
   std::vector<uint8_t> cbor(art.data, art.data + art.len);
   sezkp_buf_free(&art);
+  return write_artifact(a, cbor, bs.view.tau);
+}
+
+// write_proof_auto (io.rs:199-205): the artifact as CBOR, or as JSON unless the path ends in .cbor
+int write_artifact(const Args& a, const std::vector<uint8_t>& cbor, uint32_t tau) {
+  std::string err;
   Artifact dec;
   decode_artifact_cbor(cbor.data(), cbor.size(), dec, err);
   std::vector<uint8_t> outb = cbor;
@@ -185,7 +293,7 @@ int cmd_prove(const Args& a) {
     uint64_t domain_n = 0;
     for (int i = 7; i >= 0; i--) domain_n = (domain_n << 8) | dec.proof_bytes[i];
     std::vector<MetaEntry> meta = {{"proto", true, "stark-v1", 0}, {"domain_n", false, "", domain_n},
-                                   {"tau", false, "", bs.view.tau}};
+                                   {"tau", false, "", tau}};
     if (streaming) meta.push_back({"mode", true, "streaming", 0});
     // serde_json pretty nests the meta object one level deeper
     std::string mj = meta_to_json(meta);
@@ -251,15 +359,17 @@ int cmd_commit(const Args& a) {
   file_root(a.blocks, bs, root);
   std::vector<uint8_t> out;
   if (ext_lower(a.out) == "cbor") out = encode_manifest_cbor(root, bs.view.n_blocks);
-  else {
-    std::string s = "{\n  \"version\": 1,\n  \"root\": [\n";
-    for (int i = 0; i < 32; i++) s += "    " + std::to_string(root[i]) + (i < 31 ? ",\n" : "\n");
-    s += "  ],\n  \"n_leaves\": " + std::to_string(bs.view.n_blocks) + "\n}";
-    out.assign(s.begin(), s.end());
-  }
+  else out = manifest_json(root, bs.view.n_blocks);
   if (!write_file(a.out, out, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); return 1; }
   printf("Committed %u leaves, root=%s, wrote manifest %s\n", bs.view.n_blocks, hex(root, 32).c_str(), a.out.c_str());
   return 0;
+}
+
+std::vector<uint8_t> manifest_json(const uint8_t root[32], uint32_t n_leaves) {
+  std::string s = "{\n  \"version\": 1,\n  \"root\": [\n";
+  for (int i = 0; i < 32; i++) s += "    " + std::to_string(root[i]) + (i < 31 ? ",\n" : "\n");
+  s += "  ],\n  \"n_leaves\": " + std::to_string(n_leaves) + "\n}";
+  return std::vector<uint8_t>(s.begin(), s.end());
 }
 
 // `verify-commit` (main.rs:377-398): the precheck of prove/verify on its own
@@ -413,6 +523,8 @@ int cmd_audit(const Args& a) {
 void usage() {
   fprintf(stderr,
           "usage: sezkp-cli prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]\n"
+          "       sezkp-cli prove  --backend stark --trace T.cbor --b STEPS_PER_BLOCK --out P [--out-blocks F]\n"
+          "                        [--out-manifest F] [--manifest M] [--stream]\n"
           "       sezkp-cli verify --backend stark --blocks B --manifest M --proof P [--assume-committed] [--gpu]\n"
           "       sezkp-cli commit --blocks B --out M\n"
           "       sezkp-cli verify-commit --blocks B --manifest M\n"
@@ -438,10 +550,15 @@ int main(int argc, char** argv) {
     else if (s == "--manifest") val(a.manifest);
     else if (s == "--out" || s == "-o") val(a.out);
     else if (s == "--proof") val(a.proof);
-    else if (s == "--out-blocks" || s == "--output") val(a.out);
+    else if (s == "--out-blocks") {  // simulate's output; with prove --trace the partition beside the proof
+      val(a.out_blocks);
+      if (a.cmd != "prove") a.out = a.out_blocks;
+    } else if (s == "--output") val(a.out);
+    else if (s == "--trace") val(a.trace);
+    else if (s == "--out-manifest") val(a.out_manifest);
     else if (s == "--input") val(a.input);
     else if (s == "--t") val(a.t);
-    else if (s == "--b") val(a.b);
+    else if (s == "--b") { val(a.b); a.b_given = true; }
     else if (s == "--tau") val(a.tau);
     else if (s == "--stream") a.stream = true;
     else if (s == "--assume-committed") a.assume = true;

@@ -936,6 +936,86 @@ std::vector<uint8_t> encode_blocks_cbor(const sezkp_block_view& v) {
   return o;
 }
 
+// TraceFile (sezkp-trace format.rs:59-68) as ciborium reads and writes it:
+// map{version, tau, steps: [{input_mv, tapes: [{write, mv}]}], meta}. The
+// steps land in the store's step arrays, tau in its tau; meta is not kept.
+bool decode_trace_cbor(const uint8_t* data, size_t len, BlockStore& out, std::string& err) {
+  try {
+    Cbor d(data, len);
+    out = BlockStore();
+    uint64_t tau = 0;
+    bool have_tau = false;
+    std::vector<uint32_t> ntape;
+    int64_t r = d.begin_map();
+    while (d.more(r)) {
+      const Key k = d.key();
+      if (k == "tau") {
+        tau = d.uint();
+        if (tau > 255) throw DecodeError("tau > u8");
+        have_tau = true;
+      } else if (k == "steps") {
+        int64_t a = d.begin_array();
+        while (d.more(a)) {
+          int64_t imv = 0;
+          uint32_t nt = 0;
+          int64_t sm = d.begin_map();
+          while (d.more(sm)) {
+            const Key sk = d.key();
+            if (sk == "input_mv") {
+              imv = d.sint();
+              if (imv < -128 || imv > 127) throw DecodeError("input_mv out of i8 range");
+            } else if (sk == "tapes") {
+              int64_t ta = d.begin_array();
+              while (d.more(ta)) { decode_tape_op(d, out); nt++; }
+            } else {
+              d.skip();
+            }
+          }
+          out.input_mv.push_back((int8_t)imv);
+          ntape.push_back(nt);
+        }
+      } else {
+        d.skip();  // version, meta
+      }
+    }
+    if (!d.done()) throw DecodeError("trailing bytes after the trace");
+    if (!have_tau) throw DecodeError("trace without tau");
+    for (uint32_t t : ntape)
+      if (t != tau) throw DecodeError("step with tapes.len() != tau");
+    out.tau = (uint32_t)tau;
+    return true;
+  } catch (const std::exception& e) {
+    err = std::string("deserialize CBOR trace: ") + e.what();
+    return false;
+  }
+}
+
+// version 1 and no meta, as generate_trace leaves them (generator.rs:38-73)
+std::vector<uint8_t> encode_trace_cbor(const sezkp_trace_view& v) {
+  std::vector<uint8_t> o;
+  const uint32_t tau = v.tau;
+  o.reserve((size_t)v.t * (20 + 12 * (size_t)tau) + 32);
+  auto sint = [&](int64_t x) { if (x >= 0) cb_head(o, 0, (uint64_t)x); else cb_head(o, 1, (uint64_t)(-1 - x)); };
+  cb_head(o, 5, 4);
+  cb_text(o, "version"); cb_head(o, 0, 1);
+  cb_text(o, "tau"); cb_head(o, 0, tau);
+  cb_text(o, "steps"); cb_head(o, 4, v.t);
+  for (uint64_t st = 0; st < v.t; st++) {
+    cb_head(o, 5, 2);
+    cb_text(o, "input_mv"); sint(v.input_mv[st]);
+    cb_text(o, "tapes"); cb_head(o, 4, tau);
+    for (uint32_t r = 0; r < tau; r++) {
+      const size_t i = (size_t)st * tau + r;
+      cb_head(o, 5, 2);
+      cb_text(o, "write");
+      if (v.has_write[i]) cb_head(o, 0, v.wsym[i]); else o.push_back(0xf6);
+      cb_text(o, "mv"); sint(v.mv[i]);
+    }
+  }
+  cb_text(o, "meta"); o.push_back(0xf6);
+  return o;
+}
+
 bool decode_manifest_cbor(const uint8_t* data, size_t len, uint8_t root[32], uint32_t* n_leaves, std::string& err) {
   try {
     Cbor d(data, len);

@@ -200,6 +200,22 @@ __device__ __forceinline__ void b3_hash_block(const uint32_t (&m)[16], uint32_t 
 #pragma unroll
   for (int w = 0; w < 8; w++) out[w] = v[w] ^ v[8 + w];
 }
+// One block of a one-chunk message (at most 1024 bytes, counter 0): cv is IV
+// before the first block and the chaining value after each; the first block
+// takes B3_CHUNK_START, the last B3_CHUNK_END | B3_ROOT (a one-block message
+// all three: B3_ROOT_FLAGS) and its byte count as block_len, the rest of m
+// zero. After the last block cv is the hash (manifest leaves, partition.hip).
+#define B3_CHUNK_START 1u
+#define B3_CHUNK_END 2u
+#define B3_ROOT 8u
+__device__ __forceinline__ void b3_chunk_block(uint32_t (&cv)[8], const uint32_t (&m)[16], uint32_t block_len,
+                                               uint32_t flags) {
+  uint32_t v[16] = {cv[0], cv[1], cv[2], cv[3], cv[4], cv[5], cv[6], cv[7],
+                    B3_IV0, B3_IV1, B3_IV2, B3_IV3, 0, 0, block_len, flags};
+  b3_rounds<0>(v, m);
+#pragma unroll
+  for (int w = 0; w < 8; w++) cv[w] = v[w] ^ v[8 + w];
+}
 // leaf = BLAKE3(8 LE bytes of v)  (merkle.rs:150-160, fri_stream.rs:37-41)
 __device__ __forceinline__ void b3_leaf_u64(uint64_t v, uint32_t (&out)[8]) {
   uint32_t m[16] = {(uint32_t)v, (uint32_t)(v >> 32), 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0, 0};

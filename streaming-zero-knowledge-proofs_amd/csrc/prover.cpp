@@ -28,6 +28,7 @@
 #include "host_crypto.h"
 #include "prove_plan.h"
 #include "sezkp_internal.h"
+#include "trace_plan.h"
 #include "verify_plan.h"
 
 using namespace sezkp;
@@ -114,6 +115,7 @@ struct AsyncSlot {
   State state = IDLE;
   bool stop = false;
   uint8_t root[32];
+  bool root_from_trace = false;
   int32_t rc = 0;
   std::string msg;
   size_t len = 0;
@@ -135,6 +137,7 @@ struct sezkp_ctx {
   hipStream_t stc = nullptr;  // copy stream: staged uploads (sezkp_ctx_stage)
   hipEvent_t ev_fold = nullptr, ev_tail = nullptr, ev_expand = nullptr, ev_cols = nullptr;
   hipEvent_t ev_qin = nullptr, ev_qout = nullptr;  // the DEEP tables on the side stream, beside the INTT
+  hipEvent_t ev_root = nullptr;  // a trace image's manifest root on the side stream (created with the first trace)
   // Trace images, double-buffered: slot[active] feeds the proofs; stage()
   // fills slot[1 - active] on the copy stream while a proof runs, and the
   // next prove() switches to it (its kernels wait for the copy on the device).
@@ -148,12 +151,31 @@ struct sezkp_ctx {
     uint64_t* h_tab = nullptr;  // pinned staging of bw | bi | bo
     hipEvent_t ready = nullptr;
     bool image_pending = false;  // staged: raw copied (copy stream), k_trace_image not yet run
+    // An image that came as a raw movement log (upload_trace / stage_trace):
+    // bw | bi | bo and the metadata image are written by the device
+    // (partition.hip). meta: win_left | win_right | in_head_in | in_head_out |
+    // off_in | off_out, one block that can be copied home; root: the manifest
+    // root of this image (8 words). Allocated by the first trace that takes
+    // the slot; a block view staged into it later leaves them unused.
+    TraceMetaDev tm{};
+    uint8_t* meta = nullptr;
+    uint32_t* root = nullptr;
+    bool from_trace = false;
+    bool tables_pending = false;  // staged trace: k_block_tables and the manifest kernels not yet run
   };
   TraceSlot slot[2];
   int active = 0;
   bool staged = false;       // slot[1 - active] holds a staged trace not yet proved
   std::mutex stage_mu;
   std::vector<uint64_t> cur_step_start;  // shape of the uploaded trace (block boundaries)
+  // SEZKP_FLAG_ROOT_FROM_TRACE: the active image's manifest root sits behind
+  // the guard words (d_err + 8, eight words a single-device context never
+  // uses) and comes home with the column roots. root_in_err: it is there (a
+  // guard clear zeroes it, a switch of image replaces it); h_root: the host's
+  // copy of the active image's root, when it has come home.
+  bool root_in_err = false;
+  uint8_t h_root[32]{};
+  bool h_root_valid = false;
   NttTables tw{};
   // workspace of the current upload, and the previous upload's blocks kept
   // for reuse (keyed by byte size): re-uploading a trace of the same shape
@@ -459,6 +481,7 @@ struct sezkp_ctx {
       if (a.state != AsyncSlot::RUNNING) return;  // stop requested while idle
       uint8_t r[32];
       memcpy(r, a.root, 32);
+      const bool from_trace = a.root_from_trace;
       lk.unlock();
       // test hook: hold the worker back so that a stage() issued right after
       // prove_async runs before this proof starts (tests/test_gpu_parity.py)
@@ -467,7 +490,7 @@ struct sezkp_ctx {
       std::string m;
       size_t len = 0;
       try {
-        len = prove(r);
+        len = prove(from_trace ? nullptr : r);
       } catch (const Err& e) {
         rc = e.code;
         m = e.msg;
@@ -517,6 +540,7 @@ struct sezkp_ctx {
     if (ev_cols) (void)hipEventDestroy(ev_cols);
     if (ev_qin) (void)hipEventDestroy(ev_qin);
     if (ev_qout) (void)hipEventDestroy(ev_qout);
+    if (ev_root) (void)hipEventDestroy(ev_root);
     if (stc) (void)hipStreamSynchronize(stc);
     for (auto& sl : slot)
       if (sl.ready) (void)hipEventDestroy(sl.ready);
@@ -528,7 +552,23 @@ struct sezkp_ctx {
 
   // row0 / nrows: the view's step arrays hold only rows [row0, row0 + nrows)
   // (metadata and step_start still global): a sharded rank's slice
-  void upload(const sezkp_block_view& v, uint64_t row0 = 0, uint64_t nrows = ~0ull);
+  // tv != null: `v` carries only tau, n_blocks and the uniform step_start of
+  // a raw trace; the step arrays come from tv and the device partitions them
+  void upload(const sezkp_block_view& v, uint64_t row0 = 0, uint64_t nrows = ~0ull,
+              const sezkp_trace_view* tv = nullptr);
+  void upload_trace(const sezkp_trace_view& tv);
+  void stage_trace(const sezkp_trace_view& tv);
+  void alloc_trace_meta(TraceSlot& t);
+  size_t trace_meta_bytes() const { return (size_t)tau * nblk * 24 + (size_t)nblk * 16; }
+  // the four step arrays of tv (host or device memory) into slot t, async on s
+  void write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy);
+  // the active trace image's block tables, metadata, leaves and root, on the
+  // prover stream, synchronised; throws prove's message when a head leaves i32
+  void run_trace_tables();
+  TraceSlot& require_trace_image(const char* who);
+  void trace_manifest_root(int32_t frontier, uint8_t out[32]);
+  void trace_manifest_leaves(uint8_t* out32, uint64_t max_leaves);
+  void trace_blocks(const sezkp_trace_view* steps, BlockStore& out);
   // stage the next trace (same shape) into the spare slot on the copy stream
   void stage(const sezkp_block_view& v);
   void alloc_slot(TraceSlot& t);
@@ -540,6 +580,7 @@ struct sezkp_ctx {
   void check_shape_same(const sezkp_block_view& v) const;
   void take_staged();
   // proves into the pinned staging buffer; returns its size (bytes at h_proof)
+  // root == null: the root of the active trace image (SEZKP_FLAG_ROOT_FROM_TRACE)
   size_t prove(const uint8_t root[32]);
   // the prover with the host transcript (three round trips: column roots,
   // layer-0 root, FRI roots)
@@ -562,6 +603,7 @@ static bool hook_match(const char* spec, int rank, const char* name) {
 }
 // test hook: SEZKP_DEBUG_FAIL_AT=<rank>:<collective> makes that rank fail
 // right before that collective of every sharded prove (tests/test_gpu_sharded.py)
+static std::string head_range_msg(const std::string& who);
 static void fail_point(int rank, const char* name) {
   static const char* spec = getenv("SEZKP_DEBUG_FAIL_AT");
   if (!hook_match(spec, rank, name)) return;
@@ -636,9 +678,10 @@ static const sezkp_block_view& drop_empty_blocks(const sezkp_block_view& in, Non
   return v;
 }
 
-void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nrows) {
+void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nrows, const sezkp_trace_view* tv) {
   NonEmptyBlocks keep;
-  const sezkp_block_view& v = drop_empty_blocks(v_in, keep);
+  // (a partition has no block of zero steps, and its view no step ranges)
+  const sezkp_block_view& v = tv ? v_in : drop_empty_blocks(v_in, keep);
   HIP_OR_THROW(hipSetDevice(device));
   // a stage() may still be copying into / transposing a slot on the copy
   // stream: it must finish before its buffers become spares for this upload
@@ -658,7 +701,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   } catch (const PlanError& e) {
     throw Err{SEZKP_E_INVALID, e.msg};
   }
-  for (uint32_t k = 0; k < nblk; k++) {
+  for (uint32_t k = 0; k < nblk && !tv; k++) {
     if (v.step_hi[k] < v.step_lo[k] || v.step_hi[k] - v.step_lo[k] >= (1ULL << 28))
       throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step range [" + std::to_string(v.step_lo[k]) +
                                      ", " + std::to_string(v.step_hi[k]) + "] is empty or longer than 2^28"};
@@ -717,13 +760,24 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     hipEvent_t keep = slot[1].ready;
     slot[1] = TraceSlot{};
     slot[1].ready = keep;
+    keep = slot[0].ready;  // slot 0's buffers went to the spares with the rest of the workspace
+    slot[0] = TraceSlot{};
+    slot[0].ready = keep;
   }
+  root_in_err = false;
+  h_root_valid = false;
   alloc_slot(slot[0]);
   uint64_t* d_bs = dalloc<uint64_t>(nblk + 1);
   up(d_bs, v.step_start, nblk + 1);
   cur_step_start.assign(v.step_start, v.step_start + nblk + 1);
-  write_trace(slot[0], v, st, row0, nrows);
-  HIP_OR_THROW(hipStreamSynchronize(st));
+  if (tv) {
+    // the one synchronisation of a trace upload is run_trace_tables' below
+    alloc_trace_meta(slot[0]);
+    write_trace_steps(slot[0], *tv, st, false);
+  } else {
+    write_trace(slot[0], v, st, row0, nrows);
+    HIP_OR_THROW(hipStreamSynchronize(st));
+  }
   TraceSlot& t0 = slot[0];
   T.n = n;
   T.tau = (int)tau;
@@ -917,8 +971,296 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   h_chal = halloc<DevChal>(1);
   d_dict_of = dalloc<uint32_t>((size_t)ncols);
   up(d_dict_of, dict_of.data(), dict_of.size());
+  if (tv) {
+    // partition on the device: heads, block tables, metadata, manifest (a
+    // head outside i32 fails here, with the context left without a trace)
+    slot[0].from_trace = true;
+    slot[0].tables_pending = true;
+    HIP_OR_THROW(hipStreamSynchronize(nullptr));  // the memsets above, before the prover stream writes behind them
+    run_trace_tables();
+  }
   release_spares();
   loaded = true;
+}
+
+// ---- a trace uploaded as a raw movement log (sezkp_ctx_upload_trace)
+namespace {
+// answered before any device call; the shape errors are plan_shape's
+void check_trace_view(const sezkp_trace_view* tv) {
+  if (!tv) throw Err{SEZKP_E_INVALID, "null argument"};
+  if (tv->b == 0) throw Err{SEZKP_E_INVALID, "trace view: b (steps per block) must be at least 1"};
+  if (tv->tau > 255)  // TraceFile::tau is a u8 (format.rs:63)
+    throw Err{SEZKP_E_INVALID, "trace view: tau must be at most 255 (got " + std::to_string(tv->tau) + ")"};
+  if (tv->t && (!tv->input_mv || (tv->tau && (!tv->mv || !tv->has_write || !tv->wsym))))
+    throw Err{SEZKP_E_INVALID, "trace view: null step array"};
+  if (trace_nblk(tv->t, tv->b) > 0xFFFFFFFFull)
+    throw Err{SEZKP_E_INVALID, "trace view: more than 2^32 - 1 blocks"};
+  try {  // the row count's checks, before the block boundaries are written out
+    const uint64_t one[2] = {0, tv->t};
+    (void)plan_shape(tv->tau, one, 1, 0, 0, false);
+  } catch (const PlanError& e) {
+    throw Err{SEZKP_E_INVALID, e.msg};
+  }
+}
+std::vector<uint64_t> uniform_step_start(uint64_t t, uint64_t b) {
+  const uint64_t nb = trace_nblk(t, b);
+  std::vector<uint64_t> ss((size_t)nb + 1);
+  for (uint64_t k = 0; k <= nb; k++) ss[(size_t)k] = trace_step_start(k, t, b);
+  return ss;
+}
+// where a caller's array lives: a trace produced on the GPU is copied device
+// to device; a pointer the runtime does not know is pageable host memory
+bool on_device(const void* p, int device) {
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // not an error of ours
+    return false;
+  }
+  if (a.type != hipMemoryTypeDevice) return false;
+  if (a.device != device)
+    throw Err{SEZKP_E_INVALID, "trace view: a step array lives on device " + std::to_string(a.device) +
+                                   ", the context on device " + std::to_string(device)};
+  return true;
+}
+}  // namespace
+
+void sezkp_ctx::alloc_trace_meta(TraceSlot& t) {
+  if (!ev_root) HIP_OR_THROW(hipEventCreateWithFlags(&ev_root, hipEventDisableTiming));
+  if (t.meta) return;
+  const size_t nt = (size_t)tau * nblk;
+  t.meta = dalloc<uint8_t>(trace_meta_bytes());
+  TraceMetaDev& m = t.tm;
+  m.win_left = reinterpret_cast<int64_t*>(t.meta);
+  m.win_right = m.win_left + nt;
+  m.in_head_in = m.win_right + nt;
+  m.in_head_out = m.in_head_in + nblk;
+  m.off_in = reinterpret_cast<uint32_t*>(m.in_head_out + nblk);
+  m.off_out = m.off_in + nt;
+  m.leaves = dalloc<uint32_t>((size_t)nblk * 8);
+  m.blk_sum = dalloc<int64_t>(nblk);
+  m.tile_sum = dalloc<int64_t>((size_t)trace_scan_tiles(nblk) + 1);
+  const uint64_t scratch = manifest_tree_scratch_nodes(nblk);
+  m.lvl = scratch ? dalloc<uint32_t>((size_t)scratch * 8) : nullptr;
+  t.root = dalloc<uint32_t>(8);
+}
+
+void sezkp_ctx::write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy) {
+  const size_t cells = (size_t)tau * n;
+  wait_copy_stream();
+  HIP_OR_THROW(hipEventSynchronize(t.ready));
+  constexpr size_t chunk = (size_t)4 << 20;  // host sources: as write_trace
+  auto cp = [&](void* dst, const void* src, size_t bytes) {
+    if (!bytes) return;
+    // the kind is named once it is known: the copies of pinned host arrays
+    // then take the same path as write_trace's
+    const bool dev = on_device(src, device);
+    const size_t step = dev ? bytes : chunk;
+    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
+    for (size_t o = 0; o < bytes;) {
+      const size_t b = std::min(step, bytes - o);
+      HIP_OR_THROW(hipMemcpyAsync((uint8_t*)dst + o, (const uint8_t*)src + o, b, kind, s));
+      o += b;
+    }
+  };
+  cp(t.raw, tv.wsym, cells * 2);
+  cp(t.raw + 2 * cells, tv.mv, cells);
+  cp(t.raw + 3 * cells, tv.has_write, cells);
+  cp(t.imv, tv.input_mv, n);
+  t.tm.t = tv.t;
+  t.tm.b = tv.b;
+  if (staged_copy) t.image_pending = true;
+  else launch_image(t, s, 0, n);
+}
+
+void sezkp_ctx::upload_trace(const sezkp_trace_view& tv) {
+  if (sharded())
+    throw Err{SEZKP_E_INVALID, "upload_trace: not on a sharded context (partition the trace and upload its blocks)"};
+  check_trace_view(&tv);
+  const std::vector<uint64_t> ss = uniform_step_start(tv.t, tv.b);
+  sezkp_block_view v{};
+  v.n_blocks = (uint32_t)(ss.size() - 1);
+  v.tau = tv.tau;
+  v.step_start = ss.data();
+  upload(v, 0, ~0ull, &tv);
+}
+
+void sezkp_ctx::stage_trace(const sezkp_trace_view& tv) {
+  if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded: the first trace of a shape goes through upload"};
+  if (sharded()) throw Err{SEZKP_E_INVALID, "stage_trace: not on a sharded context"};
+  check_trace_view(&tv);
+  // the shape check of stage(): tau, block count and block boundaries
+  if (tv.tau != tau || trace_nblk(tv.t, tv.b) != nblk)
+    throw Err{SEZKP_E_INVALID, "staged trace has another shape (tau / block count): call sezkp_ctx_upload"};
+  for (uint64_t k = 0; k <= nblk; k++)
+    if (trace_step_start(k, tv.t, tv.b) != cur_step_start[(size_t)k])
+      throw Err{SEZKP_E_INVALID, "staged trace has other block boundaries: call sezkp_ctx_upload"};
+  HIP_OR_THROW(hipSetDevice(device));
+  std::lock_guard<std::mutex> lk(stage_mu);
+  if (!stc) HIP_OR_THROW(hipStreamCreateWithFlags(&stc, hipStreamNonBlocking));
+  TraceSlot& t = slot[1 - active];
+  if (!t.imv) alloc_slot(t);
+  alloc_trace_meta(t);
+  staged = false;
+  write_trace_steps(t, tv, stc, true);
+  t.from_trace = true;
+  t.tables_pending = true;
+  staged = true;
+}
+
+// Partition the active trace image and commit its manifest, synchronously on
+// the prover stream: upload_trace, a report on an image whose proof did not
+// get that far, and the proofs of traces of more than 40 tapes (the host
+// hashes their leaves: trace_plan.h). Every other proof of a staged trace runs
+// the same launches inside its own schedule (prove_body, enqueue_A).
+void sezkp_ctx::run_trace_tables() {
+  TraceSlot& t = slot[active];
+  HIP_OR_THROW(hipSetDevice(device));
+  HIP_OR_THROW(launch_expand(st, T, 0, nblk, d_err));
+  HIP_OR_THROW(launch_block_tables(st, T, t.tm, t.bw, t.bi, t.bo));
+  HIP_OR_THROW(launch_inhead_scan(st, T.input_mv, t.tm, nblk));
+  if (manifest_leaf_on_device(tau)) {
+    HIP_OR_THROW(launch_manifest_leaves(st, t.tm, tau, nblk));
+  } else {
+    std::vector<uint8_t> meta(trace_meta_bytes()), lv((size_t)nblk * 32);
+    HIP_OR_THROW(hipMemcpyAsync(meta.data(), t.meta, meta.size(), hipMemcpyDeviceToHost, st));
+    HIP_OR_THROW(hipStreamSynchronize(st));
+    const size_t nt = (size_t)tau * nblk;
+    const int64_t* wl = reinterpret_cast<const int64_t*>(meta.data());
+    const int64_t *wr = wl + nt, *ihi = wr + nt, *iho = ihi + nblk;
+    const uint32_t* oi = reinterpret_cast<const uint32_t*>(iho + nblk);
+    const uint32_t* oo = oi + nt;
+    std::vector<uint8_t> msg(manifest_leaf_len(tau));
+    for (uint32_t k = 0; k < nblk; k++) {
+      const size_t o = (size_t)k * tau;
+      const LeafFields f{k, t.tm.t, t.tm.b, tau, ihi[k], iho[k], wl + o, wr + o, oi + o, oo + o};
+      manifest_leaf_message(f, msg.data());
+      Blake3 h;
+      h.update(msg.data(), msg.size());
+      h.finalize(lv.data() + 32 * (size_t)k, 32);
+    }
+    HIP_OR_THROW(hipMemcpyAsync(t.tm.leaves, lv.data(), lv.size(), hipMemcpyHostToDevice, st));
+    HIP_OR_THROW(hipStreamSynchronize(st));  // lv leaves scope
+  }
+  HIP_OR_THROW(launch_manifest_tree(st, t.tm, nblk, t.root, d_err + 8));
+  // the guard word and the root behind it: one copy
+  uint32_t g[16];
+  HIP_OR_THROW(hipMemcpyAsync(g, d_err, sizeof g, hipMemcpyDeviceToHost, st));
+  HIP_OR_THROW(hipStreamSynchronize(st));
+  if (g[0]) {
+    root_in_err = false;
+    hipError_t me = hipMemsetAsync(d_err, 0, 64, st);
+    if (me == hipSuccess) me = hipStreamSynchronize(st);
+    if (me != hipSuccess) {
+      broken = true;
+      throw Err{SEZKP_E_DEVICE, std::string("guard word tripped (code ") + std::to_string(g[0]) +
+                                    ") and clearing it failed: " + hipGetErrorString(me) + "; the context is unusable"};
+    }
+    const std::string who = " on rank " + std::to_string(rank);
+    if (g[0] & GUARD_HEAD_RANGE) throw Err{SEZKP_E_INVALID, head_range_msg(who)};
+    throw Err{SEZKP_E_DEVICE, "guard word tripped" + who + " (code " + std::to_string(g[0]) + ")"};
+  }
+  t.tables_pending = false;
+  root_in_err = true;
+  memcpy(h_root, g + 8, 32);
+  h_root_valid = true;
+}
+
+sezkp_ctx::TraceSlot& sezkp_ctx::require_trace_image(const char* who) {
+  if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded"};
+  if (broken) throw Err{SEZKP_E_DEVICE, "context unusable: an earlier call could not clear a tripped guard word"};
+  {
+    std::lock_guard<std::mutex> lk(stage_mu);
+    if (staged)
+      throw Err{SEZKP_E_INVALID, std::string(who) + ": a staged trace is pending (prove first: this reports the image "
+                                                    "the proofs read)"};
+  }
+  TraceSlot& t = slot[active];
+  if (!t.from_trace)
+    throw Err{SEZKP_E_INVALID, std::string(who) + ": the active trace image was uploaded as blocks"};
+  if (t.tables_pending) run_trace_tables();
+  return t;
+}
+
+void sezkp_ctx::trace_manifest_leaves(uint8_t* out32, uint64_t max_leaves) {
+  TraceSlot& t = require_trace_image("manifest_leaves");
+  if (max_leaves < nblk)
+    throw Err{SEZKP_E_INVALID, "manifest_leaves: room for " + std::to_string(max_leaves) + " leaves, the trace has " +
+                                   std::to_string(nblk) + " blocks"};
+  HIP_OR_THROW(hipSetDevice(device));
+  HIP_OR_THROW(hipMemcpyAsync(out32, t.tm.leaves, (size_t)nblk * 32, hipMemcpyDeviceToHost, st));
+  HIP_OR_THROW(hipStreamSynchronize(st));
+}
+
+void sezkp_ctx::trace_manifest_root(int32_t frontier, uint8_t out[32]) {
+  TraceSlot& t = require_trace_image("manifest_root");
+  if (frontier) {  // Frontier (lib.rs:167-208): rare, .jsonl manifests only; from the leaves on the host
+    std::vector<uint8_t> lv((size_t)nblk * 32);
+    trace_manifest_leaves(lv.data(), nblk);
+    merkle_root_of_leaves(lv.data(), nblk, true, out);
+    return;
+  }
+  if (!h_root_valid) {
+    HIP_OR_THROW(hipSetDevice(device));
+    HIP_OR_THROW(hipMemcpyAsync(h_root, t.root, 32, hipMemcpyDeviceToHost, st));
+    HIP_OR_THROW(hipStreamSynchronize(st));
+    h_root_valid = true;
+  }
+  memcpy(out, h_root, 32);
+}
+
+// the blocks partition_trace returns for the active image: the scalar fields
+// follow from (t, b), the rest is the device's metadata image; the step
+// arrays from `steps` (host or device memory) or back from the device
+void sezkp_ctx::trace_blocks(const sezkp_trace_view* steps, BlockStore& s) {
+  TraceSlot& t = require_trace_image("trace_blocks");
+  if (steps) {
+    check_trace_view(steps);
+    if (steps->t != t.tm.t || steps->tau != tau)
+      throw Err{SEZKP_E_INVALID, "trace_blocks: the step arrays given are of another shape than the image"};
+  }
+  HIP_OR_THROW(hipSetDevice(device));
+  const size_t nt = (size_t)tau * nblk, cells = (size_t)tau * n;
+  s = BlockStore();
+  s.tau = tau;
+  s.version.assign(nblk, 1);
+  s.ctrl_in.assign(nblk, 0);
+  s.ctrl_out.assign(nblk, 0);
+  s.block_id.resize(nblk);
+  s.step_lo.resize(nblk);
+  s.step_hi.resize(nblk);
+  s.step_start = cur_step_start;
+  for (uint32_t k = 0; k < nblk; k++) {
+    s.block_id[k] = k + 1;
+    s.step_lo[k] = cur_step_start[k] + 1;
+    s.step_hi[k] = cur_step_start[(size_t)k + 1];
+  }
+  s.win_left.resize(nt);
+  s.win_right.resize(nt);
+  s.off_in.resize(nt);
+  s.off_out.resize(nt);
+  s.in_head_in.resize(nblk);
+  s.in_head_out.resize(nblk);
+  s.input_mv.resize(n);
+  s.mv.resize(cells);
+  s.has_write.resize(cells);
+  s.wsym.resize(cells);
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    if (bytes) HIP_OR_THROW(hipMemcpyAsync(dst, src, bytes, hipMemcpyDefault, st));
+  };
+  get(s.win_left.data(), t.tm.win_left, nt * 8);
+  get(s.win_right.data(), t.tm.win_right, nt * 8);
+  get(s.in_head_in.data(), t.tm.in_head_in, (size_t)nblk * 8);
+  get(s.in_head_out.data(), t.tm.in_head_out, (size_t)nblk * 8);
+  get(s.off_in.data(), t.tm.off_in, nt * 4);
+  get(s.off_out.data(), t.tm.off_out, nt * 4);
+  // the image's own copy of the step arrays is the row-major one the upload
+  // left in `raw` (wsym | mv | has_write, as the caller gave them)
+  get(s.wsym.data(), steps ? (const void*)steps->wsym : (const void*)t.raw, cells * 2);
+  get(s.mv.data(), steps ? (const void*)steps->mv : (const void*)(t.raw + 2 * cells), cells);
+  get(s.has_write.data(), steps ? (const void*)steps->has_write : (const void*)(t.raw + 3 * cells), cells);
+  get(s.input_mv.data(), steps ? (const void*)steps->input_mv : (const void*)t.imv, n);
+  HIP_OR_THROW(hipStreamSynchronize(st));
+  s.bind();
 }
 
 void sezkp_ctx::alloc_slot(TraceSlot& t) {
@@ -966,6 +1308,8 @@ void sezkp_ctx::launch_image(TraceSlot& t, hipStream_t s, uint64_t row0, uint64_
 void sezkp_ctx::write_trace(TraceSlot& t, const sezkp_block_view& v, hipStream_t s, uint64_t row0, uint64_t nrows,
                             bool staged_copy) {
   const size_t cells = (size_t)tau * n, nt = (size_t)tau * nblk;
+  t.from_trace = false;
+  t.tables_pending = false;
   // the previous copy out of h_tab (an earlier stage into this slot) and the
   // transposition of `raw` must be done
   wait_copy_stream();
@@ -1041,6 +1385,8 @@ void sezkp_ctx::take_staged() {
   if (staged) {
     active = 1 - active;
     staged = false;
+    root_in_err = false;
+    h_root_valid = false;
     TraceSlot& t = slot[active];
     T.input_mv = t.imv;
     T.mv = t.mv;
@@ -1093,6 +1439,8 @@ void sezkp_ctx::air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t
     audit_n = n;
   }
   const AirAuditOut O{d_audit, d_audit + AUD_WORDS, d_audit + AUD_WORDS + words};
+  // a trace image whose proof did not get as far as its block tables
+  if (slot[active].tables_pending) run_trace_tables();
   HIP_OR_THROW(launch_expand(st, T, 0, nblk, d_err));
   HIP_OR_THROW(launch_air_audit(st, T, O, d_err));
   // the counters and the guard word (k_air_audit_first put it beside them): one copy
@@ -1103,6 +1451,7 @@ void sezkp_ctx::air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t
   if (guard) {
     // as prove's check_guards: clear the data-dependent flag, stream-ordered,
     // so that a later prove of a good trace on this context succeeds
+    root_in_err = false;
     hipError_t me = hipMemsetAsync(d_err, 0, 64, st);
     if (me == hipSuccess) me = hipStreamSynchronize(st);
     if (me != hipSuccess) {
@@ -1429,6 +1778,20 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     t_sync += t_last;
   };
   HIP_OR_THROW(hipSetDevice(device));
+  // ---- a trace image (upload_trace / stage_trace). mroot == null
+  // (SEZKP_FLAG_ROOT_FROM_TRACE): the image's own manifest root, which the
+  // side stream leaves behind the guard words, so it comes home with the
+  // column roots. A staged trace is partitioned once, by the proof that takes
+  // it: k_block_tables after k_expand, the manifest kernels on the side
+  // stream. More than 40 tapes: the host hashes the leaves, a round trip of
+  // its own (trace_plan.h).
+  TraceSlot& img = slot[active];
+  const bool root_dev = mroot == nullptr;
+  if (root_dev && !img.from_trace)
+    throw Err{SEZKP_E_INVALID, "manifest root from the trace: the active trace image was uploaded as blocks"};
+  if (img.tables_pending && !manifest_leaf_on_device(tau)) run_trace_tables();
+  const bool trace_tables = img.tables_pending;
+  uint8_t root_home[32];
   const int k = logN;
   const bool kprobe = opt.kernel_events, stage_ev = opt.stage_events;
   auto rec = [&](int s) {
@@ -1590,6 +1953,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       if (g) {
         // a failed clear would leave the guard set and fail every later proof
         // with this one's error: mark the context unusable instead
+        root_in_err = false;  // (the clear takes the trace image's manifest root with it)
         const hipError_t me = hipMemsetAsync(d_err, 0, 64, st);
         if (me != hipSuccess) {
           broken = true;
@@ -1647,6 +2011,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // ---- column commitments (openings.rs:306-398): this rank's chunks, then
     // every rank gathers all chunk roots and builds the outer trees
     ok(launch_expand(st, T, blk_lo, blk_cnt, d_err), "expand");
+    if (trace_tables) ok(launch_block_tables(st, T, img.tm, img.bw, img.bi, img.bo), "block_tables");
     rec(1);
     // piecewise / table / dense columns on the side stream, concurrent with the
     // (VALU-bound) dictionary columns; disjoint outer-tree leaves. (Starting
@@ -1662,6 +2027,19 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // left after the transcript's first round trip
     ok(launch_compose_terms(st2, T, Tm, row_lo, row_hi - row_lo), "compose_terms");
     HIP_OR_THROW(hipEventRecord(ev_cols, st2));
+    // the manifest of a trace image behind the columns: nothing reads the
+    // root before the copy of the column roots, so the dictionary commit and
+    // the outer trees do not wait for it (ev_root)
+    if (trace_tables) {
+      ok(launch_inhead_scan(st2, T.input_mv, img.tm, nblk), "inhead_scan");
+      ok(launch_manifest_leaves(st2, img.tm, tau, nblk), "manifest_leaves");
+      ok(launch_manifest_tree(st2, img.tm, nblk, img.root, d_err + 8), "manifest_tree");
+      HIP_OR_THROW(hipEventRecord(ev_root, st2));
+    } else if (root_dev && !root_in_err) {
+      // the root was computed by an earlier call and a guard clear took it
+      HIP_OR_THROW(hipMemcpyAsync(d_err + 8, img.root, 32, hipMemcpyDeviceToDevice, st2));
+      HIP_OR_THROW(hipEventRecord(ev_root, st2));
+    }
     // (the commit of the K <= 2 columns on a third stream beside table levels
     // 3..4 measured slower, round 6: profiles/r06/ab/dict_split_streams_ab.txt)
     if (hw_build)
@@ -1697,6 +2075,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     // and the dictionary cache's status words and the piecewise tables'
     // form words behind the 16 guard words
     // and the wide head ladder's status words behind those
+    if (trace_tables || (root_dev && !root_in_err)) HIP_OR_THROW(hipStreamWaitEvent(st, ev_root, 0));
     HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots,
                                 (size_t)ncols * 32 + 4 * (16 + (2 + HW_STAT_WORDS) * (size_t)n_dict + (size_t)ncols),
                                 hipMemcpyDeviceToHost, st));
@@ -1705,6 +2084,16 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   auto host_1 = [&]() {
     const uint32_t* colroots_h = h_small;
     check_guards(h_small + 8 * ncols + gofs, nguard);
+    if (trace_tables) img.tables_pending = false;
+    if (trace_tables || root_dev) {
+      root_in_err = true;
+      memcpy(h_root, h_small + 8 * ncols + 8, 32);
+      h_root_valid = true;
+    }
+    if (root_dev) {
+      memcpy(root_home, h_root, 32);
+      mroot = root_home;
+    }
     for (int c = 0; c < n_dict; c++) {
       st_rebuilt += h_small[8 * ncols + 16 + 2 * c];
       st_entries += h_small[8 * ncols + 16 + 2 * c + 1];
@@ -2352,6 +2741,35 @@ int32_t sezkp_ctx_upload(sezkp_ctx* ctx, const sezkp_block_view* blocks, char* e
   });
 }
 
+// ---- traces as raw movement logs (partition and manifest on the device)
+int32_t sezkp_ctx_upload_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !trace) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->upload_trace(*trace);
+  });
+}
+int32_t sezkp_ctx_stage_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !trace) throw Err{SEZKP_E_INVALID, "null argument"};
+    ctx->stage_trace(*trace);
+  });
+}
+int32_t sezkp_ctx_manifest_root(sezkp_ctx* ctx, int32_t frontier, uint8_t out[32], char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->trace_manifest_root(frontier, out);
+  });
+}
+int32_t sezkp_ctx_manifest_leaves(sezkp_ctx* ctx, uint8_t* out32, uint64_t max_leaves, char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !out32) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->trace_manifest_leaves(out32, max_leaves);
+  });
+}
+
 int32_t sezkp_ctx_upload_rows(sezkp_ctx* ctx, const sezkp_block_view* blocks, uint64_t row0, uint64_t nrows,
                               char* err, size_t err_len) {
   return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
@@ -2379,12 +2797,12 @@ int32_t sezkp_shard_rows(const uint64_t* step_start, uint32_t n_blocks, int32_t 
 
 int32_t sezkp_ctx_prove(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, sezkp_buf* proof_bytes,
                         char* err, size_t err_len) {
-  (void)flags;
+  const bool from_trace = (flags & SEZKP_FLAG_ROOT_FROM_TRACE) != 0;
   return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
-    if (!ctx || !manifest_root || !proof_bytes) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (!ctx || (!manifest_root && !from_trace) || !proof_bytes) throw Err{SEZKP_E_INVALID, "null argument"};
     require_idle(ctx);
     ctx->take_staged();
-    const size_t len = ctx->prove(manifest_root);
+    const size_t len = ctx->prove(from_trace ? nullptr : manifest_root);
     proof_bytes->data = (uint8_t*)malloc(len ? len : 1);
     if (!proof_bytes->data) throw Err{SEZKP_E_NOMEM, "out of host memory"};
     memcpy(proof_bytes->data, ctx->h_proof, len);
@@ -2437,21 +2855,21 @@ int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max
 
 int32_t sezkp_ctx_prove_borrow(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, const uint8_t** data,
                                size_t* len, char* err, size_t err_len) {
-  (void)flags;
+  const bool from_trace = (flags & SEZKP_FLAG_ROOT_FROM_TRACE) != 0;
   return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
-    if (!ctx || !manifest_root || !data || !len) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (!ctx || (!manifest_root && !from_trace) || !data || !len) throw Err{SEZKP_E_INVALID, "null argument"};
     require_idle(ctx);
     ctx->take_staged();
-    *len = ctx->prove(manifest_root);
+    *len = ctx->prove(from_trace ? nullptr : manifest_root);
     *data = ctx->h_proof;
   });
 }
 
 int32_t sezkp_ctx_prove_async(sezkp_ctx* ctx, const uint8_t manifest_root[32], uint32_t flags, char* err,
                               size_t err_len) {
-  (void)flags;
+  const bool from_trace = (flags & SEZKP_FLAG_ROOT_FROM_TRACE) != 0;
   return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
-    if (!ctx || !manifest_root) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (!ctx || (!manifest_root && !from_trace)) throw Err{SEZKP_E_INVALID, "null argument"};
     if (!ctx->loaded) throw Err{SEZKP_E_INVALID, "context has no trace: call sezkp_ctx_upload first"};
     if (!ctx->async) {
       ctx->async.reset(new AsyncSlot());
@@ -2464,7 +2882,10 @@ int32_t sezkp_ctx_prove_async(sezkp_ctx* ctx, const uint8_t manifest_root[32], u
         throw Err{SEZKP_E_INVALID, "a proof is already in flight on this context (call sezkp_ctx_wait)"};
       HIP_OR_THROW(hipSetDevice(ctx->device));
       ctx->take_staged();  // this proof's trace image is fixed before the call returns
-      memcpy(a.root, manifest_root, 32);
+      if (from_trace && !ctx->slot[ctx->active].from_trace)
+        throw Err{SEZKP_E_INVALID, "manifest root from the trace: the active trace image was uploaded as blocks"};
+      a.root_from_trace = from_trace;
+      if (!from_trace) memcpy(a.root, manifest_root, 32);
       a.state = AsyncSlot::RUNNING;
     }
     a.cv.notify_all();
@@ -2929,6 +3350,85 @@ struct sezkp_blocks {
   BlockStore s;
   std::vector<uint64_t> line_off;  // sezkp_blocks_decode_jsonl_meta: each line's byte offset
 };
+int32_t sezkp_ctx_trace_blocks(sezkp_ctx* ctx, const sezkp_trace_view* steps, sezkp_blocks** out, char* err,
+                               size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    std::unique_ptr<sezkp_blocks> b(new sezkp_blocks());
+    ctx->trace_blocks(steps, b->s);
+    *out = b.release();
+  });
+}
+
+// StarkV1::prove for a caller that holds the movement log, not the blocks:
+// partition_trace (partition.rs:43-150), commit_blocks (sezkp-merkle
+// lib.rs:214-222) and prove_v1 in one upload and one proof on device 0.
+// The argument and shape checks come before any device is touched.
+int32_t sezkp_stark_v1_prove_trace(const sezkp_trace_view* trace, uint32_t flags, sezkp_buf* proof_bytes,
+                                   uint8_t manifest_root_out[32], char* err, size_t err_len) {
+  const int32_t pre = guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!trace || !proof_bytes) throw Err{SEZKP_E_INVALID, "null argument"};
+    check_trace_view(trace);
+  });
+  if (pre != SEZKP_OK) return pre;
+  sezkp_ctx* ctx = sezkp_ctx_create(0, err, err_len);
+  if (!ctx) return SEZKP_E_DEVICE;
+  int32_t rc = sezkp_ctx_upload_trace(ctx, trace, err, err_len);
+  if (rc == SEZKP_OK)
+    rc = sezkp_ctx_prove(ctx, nullptr, flags | SEZKP_FLAG_ROOT_FROM_TRACE, proof_bytes, err, err_len);
+  if (rc == SEZKP_OK && manifest_root_out) {
+    rc = sezkp_ctx_manifest_root(ctx, 0, manifest_root_out, err, err_len);
+    if (rc != SEZKP_OK) sezkp_buf_free(proof_bytes);
+  }
+  sezkp_ctx_destroy(ctx);
+  return rc;
+}
+
+// TraceFile CBOR (sezkp-trace io.rs; format.rs:59-68)
+struct sezkp_trace {
+  BlockStore s;  // the four step arrays
+  sezkp_trace_view view{};
+};
+int32_t sezkp_trace_decode_cbor(const uint8_t* data, size_t len, sezkp_trace** out, char* err, size_t err_len) {
+  if (!out || (!data && len)) return SEZKP_E_INVALID;
+  try {
+    std::unique_ptr<sezkp_trace> t(new sezkp_trace());
+    std::string e;
+    if (!decode_trace_cbor(data, len, t->s, e)) {
+      set_err(err, err_len, e);
+      return SEZKP_E_DECODE;
+    }
+    t->view.t = t->s.input_mv.size();
+    t->view.tau = t->s.tau;
+    t->view.b = 0;
+    t->view.input_mv = t->s.input_mv.data();
+    t->view.mv = t->s.mv.data();
+    t->view.has_write = t->s.has_write.data();
+    t->view.wsym = t->s.wsym.data();
+    *out = t.release();
+    return SEZKP_OK;
+  } catch (const std::exception& e) {
+    set_err(err, err_len, e.what());
+    return SEZKP_E_NOMEM;
+  }
+}
+int32_t sezkp_trace_encode_cbor(const sezkp_trace_view* trace, sezkp_buf* out) {
+  try {
+    if (!trace || !out || trace->tau > 255 ||
+        (trace->t && (!trace->input_mv || (trace->tau && (!trace->mv || !trace->has_write || !trace->wsym)))))
+      return SEZKP_E_INVALID;
+    to_buf(encode_trace_cbor(*trace), out);
+    return SEZKP_OK;
+  } catch (const Err& e) {
+    return e.code;
+  } catch (const std::exception&) {
+    return SEZKP_E_NOMEM;
+  }
+}
+const sezkp_trace_view* sezkp_trace_view_of(const sezkp_trace* t) { return t ? &t->view : nullptr; }
+void sezkp_trace_free(sezkp_trace* t) { delete t; }
+
 int32_t sezkp_blocks_decode_jsonl_meta(const uint8_t* data, size_t len, uint64_t lo, uint64_t hi, sezkp_blocks** out,
                                        char* err, size_t err_len) {
   return sezkp_blocks_decode_jsonl_lines(data, len, lo, hi, 0, out, err, err_len);

@@ -152,6 +152,40 @@ struct TraceDev {
 };
 constexpr int64_t PW_BY_BLOCK = INT64_MIN;
 
+// A trace uploaded as a raw movement log (sezkp_ctx_upload_trace) is
+// partitioned on the device (partition.hip; the layouts in trace_plan.h).
+// The metadata image holds what partition_trace computes per block, in the
+// order of sezkp_block_view, so that it can be copied home as it is; behind
+// it the manifest leaf hashes and the scan's and the tree's scratch.
+struct TraceMetaDev {
+  uint64_t t;            // steps of the trace
+  uint32_t b;            // steps per block
+  int64_t* win_left;     // [nblk][tau]
+  int64_t* win_right;    // [nblk][tau]
+  int64_t* in_head_in;   // [nblk] input head before the block (exclusive scan of input_mv over blocks)
+  int64_t* in_head_out;  // [nblk] ... and after it
+  uint32_t* off_in;      // [nblk][tau]
+  uint32_t* off_out;     // [nblk][tau]
+  uint32_t* leaves;      // [nblk][8] manifest leaf hashes
+  int64_t* blk_sum;      // [nblk] input_mv summed per block
+  int64_t* tile_sum;     // [trace_scan_tiles(nblk)]
+  uint32_t* lvl;         // manifest_tree_scratch_nodes(nblk) nodes (null when 0)
+};
+// the largest manifest tree one workgroup reduces (k_manifest_tree)
+constexpr uint64_t MANIFEST_TREE_WG_LEAVES = 1ull << 14;
+// window lengths and head offsets of every (tape, block) from the heads of
+// launch_expand on the same stream, into bw / bi / bo ([tau][nblk]) and M
+hipError_t launch_block_tables(hipStream_t st, const TraceDev& T, const TraceMetaDev& M, uint64_t* bw, uint64_t* bi,
+                               uint64_t* bo);
+// M.in_head_in / in_head_out: per-block sums, tile sums, their scan, the add
+hipError_t launch_inhead_scan(hipStream_t st, const int8_t* input_mv, const TraceMetaDev& M, uint64_t nblk);
+// M.leaves from the metadata image (tau <= MANIFEST_LEAF_DEV_MAX_TAU)
+hipError_t launch_manifest_leaves(hipStream_t st, const TraceMetaDev& M, uint32_t tau, uint64_t nblk);
+// merkle_root of M.leaves into root_a and (when not null) root_b, 8 words each
+uint64_t manifest_tree_scratch_nodes(uint64_t nblk);
+hipError_t launch_manifest_tree(hipStream_t st, const TraceMetaDev& M, uint64_t nblk, uint32_t* root_a,
+                                uint32_t* root_b);
+
 // Per-row constraint sums of the composition (k_compose_terms): everything
 // of C(i) that does not depend on the transcript, summed over the tapes
 // exactly (integers where they are small, canonical field values otherwise).

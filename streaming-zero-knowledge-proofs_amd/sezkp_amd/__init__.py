@@ -8,6 +8,7 @@ from ._lib import LIB_PATH, SezkpError, lib  # noqa: F401  (raises ImportError i
 from .backend import (STAGES, AirAudit, ProofArtifact, ProverContext, ShardedProverContext, StarkV1,  # noqa: F401
                       VerifyResult)
 from .blocks import BlockSoA, partition, reference_blocks, reference_trace, simulate, synthetic_blocks  # noqa: F401
+from .trace import Trace  # noqa: F401
 
-__all__ = ["StarkV1", "ProverContext", "ShardedProverContext", "ProofArtifact", "AirAudit", "VerifyResult", "BlockSoA", "SezkpError", "simulate", "partition",
+__all__ = ["StarkV1", "ProverContext", "ShardedProverContext", "ProofArtifact", "AirAudit", "VerifyResult", "BlockSoA", "Trace", "SezkpError", "simulate", "partition",
            "synthetic_blocks", "reference_blocks", "reference_trace", "STAGES", "LIB_PATH", "lib"]

@@ -18,6 +18,7 @@ SEZKP_E_NOMEM = -3
 SEZKP_E_DECODE = -4
 SEZKP_E_VERIFY = -5
 SEZKP_FLAG_STREAMING = 1
+SEZKP_FLAG_ROOT_FROM_TRACE = 2
 ABI_VERSION = 4  # include/sezkp_stark.h SEZKP_ABI_VERSION: the layouts this module binds
 
 # every symbol include/sezkp_stark.h declares (checked by tests/test_abi.py)
@@ -39,6 +40,9 @@ EXPORTS = [
     "sezkp_ctx_air_audit", "sezkp_stark_v1_air_audit", "sezkp_ctx_dict_cache_stats", "sezkp_ctx_pw_table_stats",
     "sezkp_ctx_verify_batch", "sezkp_stark_v1_verify_batch", "sezkp_ctx_verify_times",
     "sezkp_ctx_head_wide_stats",
+    "sezkp_ctx_upload_trace", "sezkp_ctx_stage_trace", "sezkp_ctx_manifest_root", "sezkp_ctx_manifest_leaves",
+    "sezkp_ctx_trace_blocks", "sezkp_stark_v1_prove_trace", "sezkp_trace_decode_cbor", "sezkp_trace_encode_cbor",
+    "sezkp_trace_view_of", "sezkp_trace_free",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -117,6 +121,11 @@ class HostComm(C.Structure):
 
 class BlockView(C.Structure):
     _fields_ = [("n_blocks", C.c_uint32), ("tau", C.c_uint32)] + [(f, C.POINTER(t)) for f, t in VIEW_FIELDS]
+
+
+class TraceView(C.Structure):  # sezkp_trace_view; the arrays as addresses (host or device memory)
+    _fields_ = [("t", C.c_uint64), ("tau", C.c_uint32), ("b", C.c_uint32), ("input_mv", C.c_void_p),
+                ("mv", C.c_void_p), ("has_write", C.c_void_p), ("wsym", C.c_void_p)]
 
 
 def _one_hip_runtime() -> None:
@@ -221,6 +230,17 @@ def _load():
     L.sezkp_ctx_verify_batch.argtypes = [C.c_void_p, C.POINTER(ProofRef), C.c_uint32, C.POINTER(VerifyResultC)] + E
     L.sezkp_stark_v1_verify_batch.argtypes = [C.POINTER(ProofRef), C.c_uint32, C.POINTER(VerifyResultC)] + E
     L.sezkp_ctx_verify_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
+    L.sezkp_ctx_upload_trace.argtypes = [C.c_void_p, C.POINTER(TraceView)] + E
+    L.sezkp_ctx_stage_trace.argtypes = [C.c_void_p, C.POINTER(TraceView)] + E
+    L.sezkp_ctx_manifest_root.argtypes = [C.c_void_p, C.c_int32, C.c_char_p] + E
+    L.sezkp_ctx_manifest_leaves.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + E
+    L.sezkp_ctx_trace_blocks.argtypes = [C.c_void_p, C.POINTER(TraceView), C.POINTER(C.c_void_p)] + E
+    L.sezkp_stark_v1_prove_trace.argtypes = [C.POINTER(TraceView), C.c_uint32, C.POINTER(Buf), C.c_char_p] + E
+    L.sezkp_trace_decode_cbor.argtypes = [C.c_char_p, C.c_size_t, C.POINTER(C.c_void_p)] + E
+    L.sezkp_trace_encode_cbor.argtypes = [C.POINTER(TraceView), C.POINTER(Buf)]
+    L.sezkp_trace_view_of.restype = C.POINTER(TraceView)
+    L.sezkp_trace_view_of.argtypes = [C.c_void_p]
+    L.sezkp_trace_free.argtypes = [C.c_void_p]
     return L
 
 

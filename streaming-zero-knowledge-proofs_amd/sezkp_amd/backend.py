@@ -11,9 +11,10 @@ import json
 import struct
 from dataclasses import dataclass, field
 
-from ._lib import (AIR_FAMILIES, SEZKP_FLAG_STREAMING, VERIFY_TIMES, AirAuditC, Buf, ProofRef, SezkpError,
-                   VerifyResultC, check, lib, take_buf)
+from ._lib import (AIR_FAMILIES, SEZKP_FLAG_ROOT_FROM_TRACE, SEZKP_FLAG_STREAMING, VERIFY_TIMES, AirAuditC, Buf,
+                   ProofRef, SezkpError, VerifyResultC, check, lib, take_buf)
 from .blocks import BlockSoA
+from .trace import trace_view
 
 STAGES = ["expand", "col_commit", "col_outer", "compose", "intt", "lde_ntt", "deep", "layer0_tree",
           "layer0_upper", "fri_fold_trees", "col_openings", "fri_paths", "total",
@@ -191,6 +192,21 @@ class StarkV1:
         return ProofArtifact("stark", bytes(manifest_root), proof, meta)
 
     @staticmethod
+    def prove_trace(input_mv, mv, has_write, wsym, b: int, streaming: bool = False) -> ProofArtifact:
+        """StarkV1::prove for a caller that holds the movement log: the device
+        partitions it into blocks of b steps (partition.rs:43-150), commits
+        the manifest and proves (sezkp_stark_v1_prove_trace). The artifact's
+        manifest_root is the computed one."""
+        v, _keep = trace_view(input_mv, mv, has_write, wsym, b)
+        pb = Buf()
+        root = C.create_string_buffer(32)
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_stark_v1_prove_trace(C.byref(v), SEZKP_FLAG_STREAMING if streaming else 0, C.byref(pb), root,
+                                             err, 1024), err)
+        proof = take_buf(pb)
+        return ProofArtifact("stark", root.raw, proof, _meta(proof, int(v.tau), streaming))
+
+    @staticmethod
     def verify(artifact: ProofArtifact, blocks: BlockSoA, manifest_root: bytes) -> None:
         """StarkV1::verify (lib.rs:144-162 -> v1/verify.rs:60-196), host CPU."""
         if artifact.backend != "stark":
@@ -234,6 +250,8 @@ class ProverContext:
             raise SezkpError(-2, err.value.decode())
         self.tau = 0
         self.n_rows = 0  # rows of the uploaded trace
+        self.n_blocks = 0
+        self.device = device
         self.rank, self.world = 0, 1
 
     def upload(self, blocks: BlockSoA) -> None:
@@ -242,6 +260,56 @@ class ProverContext:
         check(lib.sezkp_ctx_upload(self._h, C.byref(blocks.view()), err, 1024), err)
         self.tau = blocks.tau
         self.n_rows = int(blocks.step_start[-1])
+        self.n_blocks = blocks.n_blocks
+
+    def upload_trace(self, input_mv, mv, has_write, wsym, b: int) -> None:
+        """Upload a raw movement log (step-major numpy arrays, or contiguous
+        torch tensors on this context's device): the device partitions it into
+        blocks of b steps and commits the manifest (sezkp_ctx_upload_trace);
+        prove() then needs no root, and manifest_root() / blocks() report what
+        the device computed."""
+        v, keep = trace_view(input_mv, mv, has_write, wsym, b, getattr(self, "device", None))
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_upload_trace(self._h, C.byref(v), err, 1024), err)
+        self.tau, self.n_rows = int(v.tau), int(v.t)
+        self.n_blocks = -(-int(v.t) // int(v.b))
+        del keep  # the call is synchronous
+
+    def stage_trace(self, input_mv, mv, has_write, wsym, b: int) -> None:
+        """stage() for a raw movement log of the uploaded shape
+        (sezkp_ctx_stage_trace); the arrays must stay unchanged until the
+        prove that takes them has completed."""
+        v, keep = trace_view(input_mv, mv, has_write, wsym, b, getattr(self, "device", None))
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_stage_trace(self._h, C.byref(v), err, 1024), err)
+        self._staged = keep  # keep the arrays alive
+
+    def manifest_root(self, frontier: bool = False) -> bytes:
+        """The manifest root of the trace image the proofs read, as the device
+        computed it (sezkp_ctx_manifest_root): commit_blocks' batch root, or
+        the Frontier root of .jsonl block files."""
+        out = C.create_string_buffer(32)
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_manifest_root(self._h, 1 if frontier else 0, out, err, 1024), err)
+        return out.raw
+
+    def manifest_leaves(self) -> bytes:
+        """The manifest leaf hash of every block of the trace image, 32 bytes
+        each (sezkp_ctx_manifest_leaves)."""
+        nb = max(1, int(getattr(self, "n_blocks", 0)))
+        out = C.create_string_buffer(32 * nb)
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_manifest_leaves(self._h, out, nb, err, 1024), err)
+        return out.raw[:32 * int(self.n_blocks)]
+
+    def blocks(self) -> BlockSoA:
+        """The blocks partition_trace gives for the trace image, with the
+        metadata the device computed and the step arrays read back from it
+        (sezkp_ctx_trace_blocks)."""
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_trace_blocks(self._h, None, C.byref(h), err, 1024), err)
+        return BlockSoA._take(h)
 
     def upload_rows(self, blocks: BlockSoA, row0: int, nrows: int) -> None:
         """Upload from a view whose step arrays hold only rows [row0, row0 +
@@ -266,11 +334,17 @@ class ProverContext:
         check(lib.sezkp_ctx_stage(self._h, C.byref(blocks.view()), err, 1024), err)
         self._staged = blocks  # keep the arrays alive
 
-    def prove(self, manifest_root: bytes, streaming: bool = False) -> ProofArtifact:
+    def prove(self, manifest_root: bytes | None = None, streaming: bool = False) -> ProofArtifact:
+        """manifest_root=None: the root of the trace image, computed on the
+        device (SEZKP_FLAG_ROOT_FROM_TRACE; needs upload_trace / stage_trace)."""
         pb = Buf()
         err = C.create_string_buffer(1024)
-        check(lib.sezkp_ctx_prove(self._h, bytes(manifest_root), SEZKP_FLAG_STREAMING if streaming else 0,
-                                  C.byref(pb), err, 1024), err)
+        flags = SEZKP_FLAG_STREAMING if streaming else 0
+        if manifest_root is None:
+            check(lib.sezkp_ctx_prove(self._h, None, flags | SEZKP_FLAG_ROOT_FROM_TRACE, C.byref(pb), err, 1024), err)
+            manifest_root = self.manifest_root()
+        else:
+            check(lib.sezkp_ctx_prove(self._h, bytes(manifest_root), flags, C.byref(pb), err, 1024), err)
         proof = take_buf(pb)
         return ProofArtifact("stark", bytes(manifest_root), proof, _meta(proof, self.tau, streaming))
 
@@ -313,19 +387,26 @@ class ProverContext:
         n = lib.sezkp_ctx_verify_times(self._h, buf, len(VERIFY_TIMES))
         return {VERIFY_TIMES[i]: buf[i] for i in range(n)}
 
-    def prove_view(self, manifest_root: bytes) -> memoryview:
+    def prove_view(self, manifest_root: bytes | None = None) -> memoryview:
         """The proof bytes as a read-only view of the context's pinned host
-        buffer (no copy); valid until the next prove/upload/close."""
+        buffer (no copy); valid until the next prove/upload/close.
+        manifest_root=None: the trace image's own root, as prove()."""
         ptr = C.POINTER(C.c_uint8)()
         n = C.c_size_t()
         err = C.create_string_buffer(1024)
-        check(lib.sezkp_ctx_prove_borrow(self._h, bytes(manifest_root), 0, C.byref(ptr), C.byref(n), err, 1024), err)
+        root = None if manifest_root is None else bytes(manifest_root)
+        flags = SEZKP_FLAG_ROOT_FROM_TRACE if manifest_root is None else 0
+        check(lib.sezkp_ctx_prove_borrow(self._h, root, flags, C.byref(ptr), C.byref(n), err, 1024), err)
         return memoryview((C.c_uint8 * n.value).from_address(C.addressof(ptr.contents))).cast("B").toreadonly()
 
-    def prove_async(self, manifest_root: bytes) -> None:
-        """Start a proof on the context's worker thread (sezkp_ctx_prove_async)."""
+    def prove_async(self, manifest_root: bytes | None = None) -> None:
+        """Start a proof on the context's worker thread (sezkp_ctx_prove_async);
+        manifest_root=None: the trace image's own root, as prove()."""
         err = C.create_string_buffer(1024)
-        check(lib.sezkp_ctx_prove_async(self._h, bytes(manifest_root), 0, err, 1024), err)
+        if manifest_root is None:
+            check(lib.sezkp_ctx_prove_async(self._h, None, SEZKP_FLAG_ROOT_FROM_TRACE, err, 1024), err)
+        else:
+            check(lib.sezkp_ctx_prove_async(self._h, bytes(manifest_root), 0, err, 1024), err)
 
     def wait_view(self) -> memoryview:
         """Wait for the proof started by prove_async; a borrowed view as prove_view."""

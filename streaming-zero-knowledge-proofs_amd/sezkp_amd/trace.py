@@ -1,0 +1,120 @@
+"""Movement logs (`TraceFile`, crates/sezkp-trace/src/format.rs:59-68) as
+step-major arrays, the input of `ProverContext.upload_trace` /
+`StarkV1.prove_trace`: the device partitions them and commits the manifest
+(sezkp_ctx_upload_trace), so no BlockSoA is built on the host.
+
+The four arrays are input_mv[t] (i8), mv[t, tau] (i8), has_write[t, tau] (u8)
+and wsym[t, tau] (u16), as `simulate()` / `reference_trace()` return them:
+numpy arrays, or contiguous torch tensors on the context's device (a trace
+produced by a simulator on the GPU goes over without a trip through the host).
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from ._lib import Buf, SezkpError, TraceView, lib, take_buf
+
+_NP_TYPES = (np.int8, np.int8, np.uint8, np.uint16)
+_NAMES = ("input_mv", "mv", "has_write", "wsym")
+
+
+def _is_torch(a) -> bool:
+    return type(a).__module__.split(".")[0] == "torch"
+
+
+def trace_view(input_mv, mv, has_write, wsym, b: int, device: int | None = None):
+    """(TraceView, keep): the sezkp_trace_view of the four arrays with block
+    size b, and the objects that must stay alive while the view is used.
+    Torch tensors must be contiguous, of the right width and (when `device` is
+    given) on that device; the current torch stream of their device is
+    synchronised, so the library's own stream reads finished data."""
+    arrs = [input_mv, mv, has_write, wsym]
+    keep, ptrs, shapes = [], [], []
+    for name, a, npt in zip(_NAMES, arrs, _NP_TYPES):
+        if _is_torch(a):
+            import torch
+            width = {torch.int8: 1, torch.uint8: 1, torch.int16: 2, getattr(torch, "uint16", torch.int16): 2}.get(a.dtype)
+            if width != np.dtype(npt).itemsize:
+                raise SezkpError(-1, f"trace.{name}: tensor dtype {a.dtype} is not {np.dtype(npt).itemsize} byte(s) wide")
+            if not a.is_contiguous():
+                raise SezkpError(-1, f"trace.{name}: tensor must be contiguous")
+            if a.is_cuda:
+                if device is not None and a.device.index != device:
+                    raise SezkpError(-1, f"trace.{name}: tensor is on {a.device}, the context on device {device}")
+                torch.cuda.current_stream(a.device).synchronize()
+            keep.append(a)
+            ptrs.append(a.data_ptr() if a.numel() else 0)
+            shapes.append(tuple(a.shape))
+        else:
+            a = np.ascontiguousarray(a, dtype=npt)
+            keep.append(a)
+            ptrs.append(a.ctypes.data if a.size else 0)
+            shapes.append(a.shape)
+    t = int(shapes[0][0]) if len(shapes[0]) == 1 else -1
+    if t < 0 or len(shapes[1]) != 2 or shapes[1][0] != t:
+        raise SezkpError(-1, "trace: input_mv must be [t] and mv [t, tau]")
+    tau = int(shapes[1][1])
+    for name, sh in zip(_NAMES[2:], shapes[2:]):
+        if tuple(sh) != (t, tau):
+            raise SezkpError(-1, f"trace.{name} has shape {tuple(sh)}, expected {(t, tau)}")
+    if not 0 <= int(b) < 1 << 32:
+        raise SezkpError(-1, "trace: b must fit 32 bits")
+    v = TraceView()
+    v.t, v.tau, v.b = t, tau, int(b)
+    v.input_mv, v.mv, v.has_write, v.wsym = [p or None for p in ptrs]
+    return v, keep
+
+
+class Trace:
+    """A TraceFile held as the four step-major numpy arrays."""
+
+    def __init__(self, input_mv, mv, has_write, wsym):
+        self.input_mv = np.ascontiguousarray(input_mv, dtype=np.int8)
+        self.mv = np.ascontiguousarray(mv, dtype=np.int8)
+        self.has_write = np.ascontiguousarray(has_write, dtype=np.uint8)
+        self.wsym = np.ascontiguousarray(wsym, dtype=np.uint16)
+        if self.mv.ndim != 2 or self.mv.shape[0] != self.input_mv.size:
+            raise SezkpError(-1, "trace: input_mv must be [t] and mv [t, tau]")
+
+    @property
+    def t(self) -> int:
+        return int(self.input_mv.size)
+
+    @property
+    def tau(self) -> int:
+        return int(self.mv.shape[1])
+
+    def arrays(self) -> tuple:
+        return self.input_mv, self.mv, self.has_write, self.wsym
+
+    @classmethod
+    def from_cbor(cls, data: bytes) -> "Trace":
+        """Decode a TraceFile written as CBOR (sezkp_trace_decode_cbor)."""
+        h = C.c_void_p()
+        err = C.create_string_buffer(512)
+        rc = lib.sezkp_trace_decode_cbor(data, len(data), C.byref(h), err, 512)
+        if rc != 0:
+            raise SezkpError(rc, err.value.decode())
+        try:
+            v = lib.sezkp_trace_view_of(h).contents
+            t, tau = int(v.t), int(v.tau)
+
+            def arr(p, n, dt):
+                if not n:
+                    return np.zeros(0, dt)
+                return np.ctypeslib.as_array(C.cast(p, C.POINTER(np.ctypeslib.as_ctypes_type(dt))), shape=(n,)).copy()
+            return cls(arr(v.input_mv, t, np.int8), arr(v.mv, t * tau, np.int8).reshape(t, tau),
+                       arr(v.has_write, t * tau, np.uint8).reshape(t, tau), arr(v.wsym, t * tau, np.uint16).reshape(t, tau))
+        finally:
+            lib.sezkp_trace_free(h)
+
+    def to_cbor(self) -> bytes:
+        """The TraceFile as the reference writes it (sezkp_trace_encode_cbor)."""
+        v, _keep = trace_view(*self.arrays(), b=0)
+        b = Buf()
+        rc = lib.sezkp_trace_encode_cbor(C.byref(v), C.byref(b))
+        if rc != 0:
+            raise SezkpError(rc, "encode trace cbor")
+        return take_buf(b)
