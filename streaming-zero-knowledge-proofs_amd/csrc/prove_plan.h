@@ -61,8 +61,14 @@ struct ShapePlan {
   uint64_t M = 0;                    // local LDE length N / P
   int logM = 0;
   int rR = -1;  // run layers 0..rR (len >= 4096 P), the rest replicated
-  // leaves per WG of the layer-0 tree and the forest: 2048, or 1024 when the
-  // local LDE has at most 2^21 points (see sezkp_ctx::tree_wg_log)
+  // leaves per WG of the layer-0 tree and the forest: 2048 (L16M_LOG), or 1024
+  // (L16S_LOG) when the local LDE has at most 2^21 points. The 2^21 threshold
+  // was measured in round 4 (tools/r4i.sh), when the larger size was still
+  // 4096 leaves: with 1024-leaf WGs config 3 (N = 2^21, 512 WGs of 4096) in
+  // flight went 0.499 -> 0.479 ms per proof and a P = 8 rank's trees were even;
+  // at 2^22 points (a P = 4 rank) the larger WGs were faster (layer-0 tree
+  // 0.186 against 0.208 ms). Round 5 halved the larger size to 2048
+  // (shape_of_logn below).
   int tree_wg_log = L16_LOG;
   bool full_lde = false;  // P = 2: every rank computes the whole N-point LDE
   // level the run-layer WGs reduce to: the run root (12) when run roots are
@@ -452,6 +458,36 @@ inline ProofPlan plan_proof(const ShapePlan& s, const std::vector<std::string>& 
   p.max_fri_req = (size_t)NUM_QUERIES * 2 * k;
   p.max_open_req = (size_t)NUM_QUERIES * (3 + 9 * tau);
   return p;
+}
+
+// ------------------------------------------------------------ status words
+// The one small D2H copy of a proof's first phase, in u32 WORD offsets from
+// the column roots: the roots, the 16 guard words ([0] this rank's guard,
+// [8 + r] rank r's when sharded; on a single device the eight words at +8
+// hold a trace image's manifest root), then the dictionary cache's status
+// words (k_dict_plan), one word per column for the piecewise tables' form
+// (k_col_tables) and the wide head ladder's status words. The allocation, the
+// device pointers, the host buffer, the copy and its parse all read this.
+constexpr int GUARD_WORDS = 16;
+struct StatusLayout {
+  size_t roots = 0;       // 8 words per column
+  size_t guard = 0;       // GUARD_WORDS
+  size_t trace_root = 0;  // guard + 8
+  size_t dict = 0;        // 2 words per dictionary column: rebuilt, entries
+  size_t pw = 0;          // 1 word per column
+  size_t hw = 0;          // HW_STAT_WORDS per dictionary column
+  size_t total = 0;
+};
+inline StatusLayout plan_status(int ncols, int n_dict) {
+  StatusLayout s;
+  s.roots = 0;
+  s.guard = s.roots + 8 * (size_t)ncols;
+  s.trace_root = s.guard + 8;
+  s.dict = s.guard + GUARD_WORDS;
+  s.pw = s.dict + 2 * (size_t)n_dict;
+  s.hw = s.pw + (size_t)ncols;
+  s.total = s.hw + (size_t)HW_STAT_WORDS * (size_t)n_dict;
+  return s;
 }
 
 // ------------------------------------------------------ wide head ladder

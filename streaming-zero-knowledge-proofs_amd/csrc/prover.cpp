@@ -26,6 +26,7 @@
 #include "codec.h"
 #include "comm.h"
 #include "host_crypto.h"
+#include "proof_host.h"
 #include "prove_plan.h"
 #include "sezkp_internal.h"
 #include "trace_plan.h"
@@ -33,6 +34,7 @@
 
 using namespace sezkp;
 
+#define SEZKP_LOCAL __attribute__((visibility("hidden")))
 namespace {
 
 // ST_L0TREE brackets exactly one launch (k_layer16 over the LDE) so bench.py
@@ -95,10 +97,9 @@ const NttTables& tables_for_device(int dev) {
   return g_tabs.emplace(dev, t).first->second.T;
 }
 
-uint64_t rd64(const uint8_t* p) {
-  uint64_t x = 0;
-  for (int i = 7; i >= 0; i--) x = (x << 8) | p[i];
-  return x;
+std::string head_range_msg(const std::string& who) {
+  return "a block's head position leaves the i32 range" + who +
+         " (block too long for its moves: block length x max |mv| must stay below 2^31)";
 }
 }  // namespace
 
@@ -128,6 +129,129 @@ static int worker_delay_us() {
   }();
   return us;
 }
+
+struct ProveOptions;
+
+namespace {
+// ---- state that outlives an upload: allocated on demand, outside the upload
+// workspace, each with its own release (the context's destructor calls them
+// in order, before the streams go)
+
+// The dictionary tables and their reuse keys (DictCache), sized for `cols`
+// columns, so a later upload of the same shape finds the tables its columns'
+// keys name; beside them the wide head ladders (HeadWideDev): one record per
+// dictionary column in d_hw (written only by a proof that builds a ladder),
+// the ladders in d_hwtabs (allocated by the first such proof, regrown when a
+// re-span needs more), the host's state in hw_cols (prove_plan.h) and the
+// last completed prove's report in hw_stats (sezkp_ctx_head_wide_stats).
+struct DictTables {
+  uint32_t* d_dtabs = nullptr;
+  DictKey* d_dkeys = nullptr;        // one block: the keys, the per-level words, the reuse flags
+  uint64_t* d_dlvl_seq = nullptr;
+  uint32_t* d_dreuse = nullptr;
+  size_t cols = ~(size_t)0;
+  // epoch: a new value whenever a host-side input of the tables changes
+  // (hkey, shape), after a proof that did not complete (dirty) and for every
+  // proof with SEZKP_DICT_CACHE=0; seq numbers the proofs
+  uint64_t epoch = 1, seq = 0;
+  // the host-side inputs of make_plan: n, and the rows this device commits
+  // (ProofRun's row_lo / row_hi, from the rank's chunks), the hooks
+  struct HostKey {
+    uint64_t n = 0, nrows = 0, row0 = 0, plan_rows = 0;
+    uint32_t tab_cap = 0;
+    bool operator==(const HostKey& o) const {
+      return n == o.n && nrows == o.nrows && row0 == o.row0 && plan_rows == o.plan_rows && tab_cap == o.tab_cap;
+    }
+  } hkey;
+  std::vector<uint8_t> shape;   // the dictionary columns' templates and DictCols of the last upload
+  bool dirty = false;
+  uint32_t stat_rebuilt = 0, stat_reused = 0;  // last completed prove (sezkp_ctx_dict_cache_stats)
+  uint64_t stat_entries = 0;
+  HeadWideDev* d_hw = nullptr;
+  uint32_t* d_hwtabs = nullptr;
+  uint64_t hwtabs_nodes = 0;
+  std::vector<HeadWideCol> hw_cols;
+  std::vector<HeadWideDev> hw_recs;
+  std::vector<sezkp_head_wide_info> hw_stats;
+
+  // what one proof takes from the tables (begin_proof) and gives back (end_proof)
+  struct Use {
+    DictCache dcache{};
+    bool hw_build = false;           // this proof builds ladders (launch_head_ladder)
+    uint64_t hw_max_entries = 0;
+    std::vector<uint64_t> hw_built;  // per dictionary column: entries this proof builds
+  };
+  // upload: tables for nd columns (a new count drops the old ones), then the
+  // epoch moves if the columns' templates and DictCols differ from the last upload's
+  void resize(size_t nd);
+  void note_shape(std::vector<uint8_t>& shape_now);
+  // a proof's prelude: the epoch and, per head column, whether it reads its
+  // ladder and whether it builds it first; records that change go over on st
+  Use begin_proof(const HostKey& hk, const ProveOptions& opt, const std::vector<sezkp_dict_plan_info>& info,
+                  hipStream_t st, uint32_t* d_dstatus, uint32_t* d_hwstat);
+  // after a completed proof: its counts and what it saw of the head columns
+  void end_proof(const Use& use, const std::vector<sezkp_dict_plan_info>& info, const std::vector<HeadWideObs>& obs,
+                 uint32_t rebuilt, uint64_t entries);
+  void release() {
+    if (d_dtabs) (void)hipFree(d_dtabs);
+    if (d_dkeys) (void)hipFree(d_dkeys);
+    if (d_hw) (void)hipFree(d_hw);
+    if (d_hwtabs) (void)hipFree(d_hwtabs);
+    d_dtabs = nullptr;
+    d_dkeys = nullptr;
+    d_hw = nullptr;
+    d_hwtabs = nullptr;
+    hwtabs_nodes = 0;
+    hw_cols.clear();
+    hw_recs.clear();
+    cols = ~(size_t)0;
+  }
+};
+
+// AIR audit (sezkp_ctx_air_audit): the counter block (AUD_WORDS), then the
+// violating and the rejectable bitmap of (n + 63) / 64 words each. Allocated
+// by the first audit and kept while uploads keep n: outside the workspace,
+// so upload and prove allocate what they do without it.
+struct AuditBuffers {
+  uint64_t* d_audit = nullptr;
+  uint64_t* h_audit = nullptr;  // pinned: the counter block's landing place
+  uint64_t audit_n = 0;
+  void release_device() {  // an upload of another n
+    if (d_audit) (void)hipFree(d_audit);
+    d_audit = nullptr;
+    audit_n = 0;
+  }
+  void release() {
+    release_device();
+    if (h_audit) (void)hipHostFree(h_audit);
+    h_audit = nullptr;
+  }
+};
+
+// Batch verification (sezkp_ctx_verify_batch): one pinned block and its
+// device twin hold a slice's proof bytes, an aligned copy of the column
+// roots, the job table and the result words, in that order; the label
+// templates (the same for every proof) stay on the device. Like the audit's
+// buffers they live outside the upload workspace: they grow on demand and
+// are kept, and neither upload nor prove sees them.
+struct VerifyBuffers {
+  uint8_t* d_vfy = nullptr;
+  uint8_t* h_vfy = nullptr;
+  size_t vfy_cap = 0;
+  VerifyLabel* d_vlabels = nullptr;
+  uint64_t n_vlabels = 0;
+  hipEvent_t vev[4]{};
+  double vfy_ms[SEZKP_VERIFY_TIMES]{};
+  void release() {
+    if (d_vfy) (void)hipFree(d_vfy);
+    if (h_vfy) (void)hipHostFree(h_vfy);
+    if (d_vlabels) (void)hipFree(d_vlabels);
+    for (auto& e : vev)
+      if (e) (void)hipEventDestroy(e);
+    *this = VerifyBuffers{};
+  }
+};
+}  // namespace
 
 struct sezkp_ctx {
   int device = 0;
@@ -182,11 +306,10 @@ struct sezkp_ctx {
   // allocates nothing. Spares left unclaimed are freed at the end of upload.
   std::vector<std::pair<void*, size_t>> dev_allocs, host_allocs, mapped_allocs;
   std::multimap<size_t, void*> spare_dev, spare_host, spare_mapped;
-  // shape
+  // shape of the uploaded trace (prove_plan.h): n, N, tau, the rank's chunks
+  // and blocks, the tree workgroup size; rank / logP as set at create
   bool loaded = false;
-  uint64_t n = 0, N = 0;
-  int logn = 0, logN = 0, ncols = 0, logChunks = 0;
-  uint32_t tau = 0, nblk = 0;
+  ShapePlan sp;
   TraceDev T{};
   std::vector<std::string> labels;
   ColTemplate* d_tmpl = nullptr;
@@ -206,72 +329,27 @@ struct sezkp_ctx {
   DictPlan* d_dplans = nullptr;
   std::vector<sezkp_dict_plan_info> dict_info;  // col / kind / tape of each dictionary column (sezkp_ctx_dict_plans)
   bool have_plans = false;           // d_dplans holds the plans of a completed prove of this upload
-  // The dictionary tables and their reuse keys (DictCache) outlive an upload:
-  // they sit outside the workspace, sized for dict_cache_cols columns, so a
-  // later upload of the same shape finds the tables its columns' keys name.
-  uint32_t* d_dtabs = nullptr;
-  DictKey* d_dkeys = nullptr;        // one block: the keys, the per-level words, the reuse flags
-  uint64_t* d_dlvl_seq = nullptr;
-  uint32_t* d_dreuse = nullptr;
-  uint32_t* d_dstatus = nullptr;     // behind the guard words (d_err + 16): 2 words per column
-  size_t dict_cache_cols = ~(size_t)0;
-  // dict_epoch: a new value whenever a host-side input of the tables changes
-  // (dict_hkey, dict_shape), after a proof that did not complete (dict_dirty)
-  // and for every proof with SEZKP_DICT_CACHE=0; dict_seq numbers the proofs
-  uint64_t dict_epoch = 1, dict_seq = 0;
-  // the host-side inputs of make_plan: n, and the rows this device commits
-  // (prove_body's row_lo / row_hi, from the rank's chunks), the hooks
-  struct DictHostKey {
-    uint64_t n = 0, nrows = 0, row0 = 0, plan_rows = 0;
-    uint32_t tab_cap = 0;
-    bool operator==(const DictHostKey& o) const {
-      return n == o.n && nrows == o.nrows && row0 == o.row0 && plan_rows == o.plan_rows && tab_cap == o.tab_cap;
-    }
-  } dict_hkey;
-  std::vector<uint8_t> dict_shape;   // the dictionary columns' templates and DictCols of the last upload
-  bool dict_dirty = false;
-  uint32_t dstat_rebuilt = 0, dstat_reused = 0;  // last completed prove (sezkp_ctx_dict_cache_stats)
-  uint64_t dstat_entries = 0;
+  DictTables dict;
   // the per-block piecewise columns (kinds 7..9) and, of the last completed
   // prove, how many keyed their U tables by value and the units those built
   // (sezkp_ctx_pw_table_stats; TraceDev::pw_stat)
   std::vector<uint32_t> pw_blk_cols;
-  uint32_t* d_pwstat = nullptr;
   uint32_t pwstat_by_value = 0;
   uint64_t pwstat_units = 0;
-  // The wide head ladders (HeadWideDev) sit beside the dictionary tables:
-  // one record per dictionary column in d_hw (written only by a proof that
-  // builds a ladder), the ladders in d_hwtabs (allocated by the first such
-  // proof, regrown when a re-span needs more), the host's state in hw_cols
-  // (prove_plan.h) and the last completed prove's report in hw_stats
-  // (sezkp_ctx_head_wide_stats). d_hwstat: the status words, behind d_pwstat.
-  HeadWideDev* d_hw = nullptr;
-  uint32_t* d_hwtabs = nullptr;
-  uint64_t hwtabs_nodes = 0;
-  uint32_t* d_hwstat = nullptr;
-  std::vector<HeadWideCol> hw_cols;
-  std::vector<HeadWideDev> hw_recs;
-  std::vector<sezkp_head_wide_info> hw_stats;
-  void free_dict_cache() {
-    if (d_dtabs) (void)hipFree(d_dtabs);
-    if (d_dkeys) (void)hipFree(d_dkeys);
-    if (d_hw) (void)hipFree(d_hw);
-    if (d_hwtabs) (void)hipFree(d_hwtabs);
-    d_dtabs = nullptr;
-    d_dkeys = nullptr;
-    d_hw = nullptr;
-    d_hwtabs = nullptr;
-    hwtabs_nodes = 0;
-    hw_cols.clear();
-    hw_recs.clear();
-    dict_cache_cols = ~(size_t)0;
-  }
   uint32_t* d_dlev = nullptr;        // dictionary columns' chunk levels 6..9 (openings)
   std::vector<uint32_t> dict_of;     // column -> dictionary index or NO_DICT
   uint32_t* d_outer = nullptr;
-  uint32_t* d_err = nullptr;  // device-side guard word: non-zero = a kernel saw an out-of-range index
   uint64_t outer_stride = 0;
+  // The column roots and, right behind them, what comes home with them in one
+  // copy (StatusLayout SL, prove_plan.h). d_err: the guard words, non-zero = a
+  // kernel saw an out-of-range index; d_dstatus, d_pwstat, d_hwstat: the
+  // dictionary cache's, the piecewise tables' and the head ladders' status words
+  StatusLayout SL;
   uint32_t* d_colroots = nullptr;
+  uint32_t* d_err = nullptr;
+  uint32_t* d_dstatus = nullptr;
+  uint32_t* d_pwstat = nullptr;
+  uint32_t* d_hwstat = nullptr;
   uint64_t* d_base = nullptr;
   ComposeTerms Tm{};  // per-row composition sums (k_compose_terms, side stream)
   uint64_t *d_dq_part = nullptr, *d_dq_rlo = nullptr, *d_dq_rhi = nullptr, *d_dq_rhk = nullptr;  // DeepPoly
@@ -287,27 +365,12 @@ struct sezkp_ctx {
   int rank = 0, world = 1, logP = 0;
   std::unique_ptr<Comm> comm;            // non-null: the sharded algorithm (also at P = 1, see ctx_create)
   bool sharded() const { return comm != nullptr; }
-  // level the run-layer WGs reduce to: the run root (12) when run roots are
-  // allgathered, else 6 so the upper jobs build levels 7.. with every lane busy
-  int tree_stop() const { return sharded() ? L16_LOG : LSTORE_FRI; }
-  // leaves per WG of the layer-0 tree and the forest: 4096, or 1024 when the
-  // local LDE has at most 2^21 points (512 or fewer 4096-leaf WGs). Measured
-  // (round 4, tools/r4i.sh): config 3 (N = 2^21) in flight 0.499 -> 0.479 ms per
-  // proof, a P = 8 rank's trees even; at 2^22 points (a P = 4 rank) the
-  // 4096-leaf WGs were faster (layer-0 tree 0.186 against 0.208 ms)
-  int tree_wg_log = L16_LOG;
-  int wg_stop() const { return std::min(tree_stop(), tree_wg_log); }
-  uint64_t M = 0;                       // local LDE length N / P
-  int logM = 0;
-  int rR = -1;                          // run layers 0..rR (len >= 4096 P), the rest replicated
-  uint64_t ch_lo = 0, ch_hi = 0;        // this rank's column chunks
-  uint32_t blk_lo = 0, blk_cnt = 0;     // blocks overlapping this rank's rows (+ the next row)
   uint64_t* d_cyc = nullptr;            // P > 1: coset values f(3 w^(rank + P j)) (full_lde: all N values)
-  // P = 2: every rank computes the whole N-point LDE (the single-device
-  // schedule) and takes its own runs from it, instead of its coset and the
-  // all-to-all: one link carries the all-to-all's N/4 values per rank at
-  // 153 GB/s (~0.22 ms), more than the other half of the LDE costs (~0.09 ms)
-  bool full_lde = false;
+  // (ShapePlan::full_lde) P = 2: every rank computes the whole N-point LDE
+  // (the single-device schedule) and takes its own runs from it, instead of
+  // its coset and the all-to-all: one link carries the all-to-all's N/4 values
+  // per rank at 153 GB/s (~0.22 ms), more than the other half of the LDE
+  // costs (~0.09 ms)
   uint64_t* d_xbuf = nullptr;           // P > 1: all-to-all send buffer
   uint64_t* d_rep = nullptr;            // replicated layers (P > 1: first the whole layer rR)
   std::vector<uint64_t*> lvals;         // per FRI layer: this rank's values
@@ -329,8 +392,9 @@ struct sezkp_ctx {
   size_t hdr_bytes = 0;         // bincode header: domain_n, tau, col_roots
   std::vector<size_t> root_pos; // byte offset of each column root in the header
   uint8_t* h_proof = nullptr;   // pinned: header + body
-  uint32_t* h_small = nullptr;  // col roots / fri roots staging
+  uint32_t* h_small = nullptr;  // col roots + status words / fri roots staging
   size_t max_fri_req = 0, max_open_req = 0;
+  // ---- timing
   hipEvent_t ev[ST_NSTAGE + 1]{};
   double stage_ms[ST_NSTAGE + 1]{};
   // SEZKP_KERNEL_EVENTS=1: an event pair around the FRI forest launch for its
@@ -362,40 +426,12 @@ struct sezkp_ctx {
   // test hook (SEZKP_DEBUG_STALL_AFTER): a mapped word the stream waits on
   // after a collective, so that the collective looks stuck; set at destroy
   uint32_t* stall_word = nullptr;
-  // AIR audit (sezkp_ctx_air_audit): the counter block (AUD_WORDS), then the
-  // violating and the rejectable bitmap of (n + 63) / 64 words each. Allocated
-  // by the first audit and kept while uploads keep n: outside the workspace,
-  // so upload and prove allocate what they do without it.
-  uint64_t* d_audit = nullptr;
-  uint64_t* h_audit = nullptr;  // pinned: the counter block's landing place
-  uint64_t audit_n = 0;
-  void free_audit() {
-    if (d_audit) (void)hipFree(d_audit);
-    d_audit = nullptr;
-    audit_n = 0;
-  }
-
-  // Batch verification (sezkp_ctx_verify_batch): one pinned block and its
-  // device twin hold a slice's proof bytes, an aligned copy of the column
-  // roots, the job table and the result words, in that order; the label
-  // templates (the same for every proof) stay on the device. Like the audit's
-  // buffers they live outside the upload workspace: they grow on demand and
-  // are kept, and neither upload nor prove sees them.
-  uint8_t* d_vfy = nullptr;
-  uint8_t* h_vfy = nullptr;
-  size_t vfy_cap = 0;
-  VerifyLabel* d_vlabels = nullptr;
-  uint64_t n_vlabels = 0;
-  hipEvent_t vev[4]{};
-  double vfy_ms[SEZKP_VERIFY_TIMES]{};
-  void free_verify() {
-    if (d_vfy) (void)hipFree(d_vfy);
-    if (h_vfy) (void)hipHostFree(h_vfy);
-    if (d_vlabels) (void)hipFree(d_vlabels);
-    for (auto& e : vev)
-      if (e) (void)hipEventDestroy(e);
-  }
+  // ---- services
+  AuditBuffers audit;
+  VerifyBuffers vfy;
   void verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out);
+  // full-trace AIR audit of the active trace image (bitmaps: null or (n + 7) / 8 host bytes)
+  void air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits);
 
   static void* take_spare(std::multimap<size_t, void*>& m, size_t bytes) {
     auto it = m.find(bytes);
@@ -506,6 +542,8 @@ struct sezkp_ctx {
       a.cv.notify_all();
     }
   }
+  // wait for the worker, then sync the streams, then the workspace, spares,
+  // services and events, then the streams
   ~sezkp_ctx() {
     if (stall_word) __atomic_store_n(stall_word, 1u, __ATOMIC_SEQ_CST);  // release a stalled stream
     if (async) {  // let a proof in flight finish, then stop the worker
@@ -522,10 +560,9 @@ struct sezkp_ctx {
     if (stc) (void)hipStreamSynchronize(stc);
     free_all();
     release_spares();
-    free_audit();
-    free_verify();
-    free_dict_cache();
-    if (h_audit) (void)hipHostFree(h_audit);
+    audit.release();
+    vfy.release();
+    dict.release();
     for (auto& e : ev)
       if (e) (void)hipEventDestroy(e);
     for (auto& e : coll_ev) (void)hipEventDestroy(e);
@@ -550,16 +587,31 @@ struct sezkp_ctx {
     if (stall_word) (void)hipHostFree(stall_word);
   }
 
+  // ---- upload and trace images
   // row0 / nrows: the view's step arrays hold only rows [row0, row0 + nrows)
   // (metadata and step_start still global): a sharded rank's slice
   // tv != null: `v` carries only tau, n_blocks and the uniform step_start of
   // a raw trace; the step arrays come from tv and the device partitions them
   void upload(const sezkp_block_view& v, uint64_t row0 = 0, uint64_t nrows = ~0ull,
               const sezkp_trace_view* tv = nullptr);
+  // upload's sections, in order; each allocates from the workspace and binds
+  // what the planners laid out (SEZKP_LOCAL: not among the library's symbols)
+  struct SEZKP_LOCAL UploadPlans {
+    ColumnPlan cp;
+    FriPlan fp;
+    ProofPlan pp;
+  };
+  SEZKP_LOCAL UploadPlans plan_upload(const sezkp_block_view& v, uint64_t row0, uint64_t& nrows, bool from_trace);
+  SEZKP_LOCAL void upload_trace_image(const sezkp_block_view& v, uint64_t row0, uint64_t nrows,
+                                      const sezkp_trace_view* tv);
+  SEZKP_LOCAL void upload_columns(const ColumnPlan& cp);
+  SEZKP_LOCAL void upload_fri_workspace(const FriPlan& fp);
+  SEZKP_LOCAL void upload_proof_image(const ProofPlan& pp);
+  SEZKP_LOCAL void bind_trace_slot(const TraceSlot& t);  // the slot's arrays into T
   void upload_trace(const sezkp_trace_view& tv);
   void stage_trace(const sezkp_trace_view& tv);
   void alloc_trace_meta(TraceSlot& t);
-  size_t trace_meta_bytes() const { return (size_t)tau * nblk * 24 + (size_t)nblk * 16; }
+  size_t trace_meta_bytes() const { return (size_t)sp.tau * sp.nblk * 24 + (size_t)sp.nblk * 16; }
   // the four step arrays of tv (host or device memory) into slot t, async on s
   void write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy);
   // the active trace image's block tables, metadata, leaves and root, on the
@@ -579,38 +631,34 @@ struct sezkp_ctx {
   void wait_copy_stream();
   void check_shape_same(const sezkp_block_view& v) const;
   void take_staged();
+  // ---- one proof
   // proves into the pinned staging buffer; returns its size (bytes at h_proof)
   // root == null: the root of the active trace image (SEZKP_FLAG_ROOT_FROM_TRACE)
   size_t prove(const uint8_t root[32]);
-  // the prover with the host transcript (three round trips: column roots,
-  // layer-0 root, FRI roots)
-  size_t prove_body(const uint8_t root[32]);
-  // full-trace AIR audit of the active trace image (bitmaps: null or (n + 7) / 8 host bytes)
-  void air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits);
 };
 
+
+namespace {
 // SEZKP_COLL_TIMEOUT_S: how long a sharded rank waits for a stream holding
 // collectives before it aborts the communicator (default 60 s; a T = 2^22
 // proof takes ~10 ms once uploaded)
-static double coll_timeout_s() {
+double coll_timeout_s() {
   static const double t = getenv("SEZKP_COLL_TIMEOUT_S") ? atof(getenv("SEZKP_COLL_TIMEOUT_S")) : 60.0;
   return t > 0 ? t : 60.0;
 }
-static bool hook_match(const char* spec, int rank, const char* name) {
+bool hook_match(const char* spec, int rank, const char* name) {
   if (!spec) return false;
   const char* colon = strchr(spec, ':');
   return colon && atoi(spec) == rank && strcmp(colon + 1, name) == 0;
 }
 // test hook: SEZKP_DEBUG_FAIL_AT=<rank>:<collective> makes that rank fail
 // right before that collective of every sharded prove (tests/test_gpu_sharded.py)
-static std::string head_range_msg(const std::string& who);
-static void fail_point(int rank, const char* name) {
+void fail_point(int rank, const char* name) {
   static const char* spec = getenv("SEZKP_DEBUG_FAIL_AT");
   if (!hook_match(spec, rank, name)) return;
   throw Err{SEZKP_E_DEVICE, std::string("injected failure before collective ") + name + " on rank " +
                                 std::to_string(rank)};
 }
-
 
 // Blocks of zero steps (step_hi = step_lo - 1, so step_hi - step_lo + 1 wraps
 // to 0) contribute no rows: TraceColumns::build and RowIter skip them
@@ -626,7 +674,7 @@ struct NonEmptyBlocks {
   std::vector<uint64_t> step_lo, step_hi, step_start;
   std::vector<int64_t> in_head_in, in_head_out, win_left, win_right;
 };
-static const sezkp_block_view& drop_empty_blocks(const sezkp_block_view& in, NonEmptyBlocks& keep) {
+const sezkp_block_view& drop_empty_blocks(const sezkp_block_view& in, NonEmptyBlocks& keep) {
   uint32_t empty = 0;
   for (uint32_t k = 0; k < in.n_blocks; k++) {
     if (in.step_hi[k] - in.step_lo[k] + 1 != 0) continue;  // wrapping, as the reference's usize cast
@@ -678,6 +726,59 @@ static const sezkp_block_view& drop_empty_blocks(const sezkp_block_view& in, Non
   return v;
 }
 
+// Block k's step range against its steps in the movement log. The kernels
+// index the step arrays through step_start: every block must hold
+// step_hi - step_lo + 1 >= 1 steps (no wrap-around; the blocks of zero steps,
+// whose range wraps to 0, are gone already). upload and stage word the
+// failure each in its own way.
+enum class StepRange { ok, empty_or_long, other_length };
+StepRange check_step_range(const sezkp_block_view& v, uint32_t k) {
+  if (v.step_hi[k] < v.step_lo[k] || v.step_hi[k] - v.step_lo[k] >= (1ULL << 28)) return StepRange::empty_or_long;
+  if (v.step_hi[k] - v.step_lo[k] + 1 != v.step_start[k + 1] - v.step_start[k]) return StepRange::other_length;
+  return StepRange::ok;
+}
+
+template <class D, class S>
+void up(D* dst, const S* src, size_t count) {
+  if (count) HIP_OR_THROW(hipMemcpy(dst, src, count * sizeof(*src), hipMemcpyHostToDevice));
+}
+
+// An array over in copies of at most `step` bytes, async on s. Host sources
+// go in copies of <= 4 MB (COPY_CHUNK), so a proof's D2H copy queued on the
+// same copy engine waits for one chunk, not for the rest of a 67 MB upload
+// (round 3, tools/ab_upload_chunk.sh: host -> proof 7.89 -> 7.94e9, within
+// the run-to-run spread)
+constexpr size_t COPY_CHUNK = (size_t)4 << 20;
+void copy_chunked(void* dst, const void* src, size_t bytes, size_t step, hipMemcpyKind kind, hipStream_t s) {
+  for (size_t o = 0; o < bytes;) {
+    const size_t b = std::min(step, bytes - o);
+    HIP_OR_THROW(hipMemcpyAsync((uint8_t*)dst + o, (const uint8_t*)src + o, b, kind, s));
+    o += b;
+  }
+}
+
+std::vector<uint64_t> uniform_step_start(uint64_t t, uint64_t b) {
+  const uint64_t nb = trace_nblk(t, b);
+  std::vector<uint64_t> ss((size_t)nb + 1);
+  for (uint64_t k = 0; k <= nb; k++) ss[(size_t)k] = trace_step_start(k, t, b);
+  return ss;
+}
+// where a caller's array lives: a trace produced on the GPU is copied device
+// to device; a pointer the runtime does not know is pageable host memory
+bool on_device(const void* p, int device) {
+  hipPointerAttribute_t a{};
+  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
+    (void)hipGetLastError();  // not an error of ours
+    return false;
+  }
+  if (a.type != hipMemoryTypeDevice) return false;
+  if (a.device != device)
+    throw Err{SEZKP_E_INVALID, "trace view: a step array lives on device " + std::to_string(a.device) +
+                                   ", the context on device " + std::to_string(device)};
+  return true;
+}
+}  // namespace
+
 void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nrows, const sezkp_trace_view* tv) {
   NonEmptyBlocks keep;
   // (a partition has no block of zero steps, and its view no step ranges)
@@ -690,70 +791,75 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   if (st2 != st) HIP_OR_THROW(hipStreamSynchronize(st2));
   if (stc) HIP_OR_THROW(hipStreamSynchronize(stc));
   free_all(true);
-  tau = v.tau;
-  nblk = v.n_blocks;
-  // the kernels index the step arrays through step_start: it must start at 0
-  // and every block must hold step_hi - step_lo + 1 >= 1 steps (no wrap-around;
-  // the blocks of zero steps, whose range wraps to 0, are gone already); the
+  const UploadPlans p = plan_upload(v, row0, nrows, tv != nullptr);
+  upload_trace_image(v, row0, nrows, tv);
+  upload_columns(p.cp);
+  upload_fri_workspace(p.fp);
+  upload_proof_image(p.pp);
+  if (tv) {
+    // partition on the device: heads, block tables, metadata, manifest (a
+    // head outside i32 fails here, with the context left without a trace)
+    slot[0].from_trace = true;
+    slot[0].tables_pending = true;
+    // upload_columns' memsets of the guard and status words (null stream),
+    // before the prover stream writes behind them
+    HIP_OR_THROW(hipStreamSynchronize(nullptr));
+    run_trace_tables();
+  }
+  release_spares();
+  loaded = true;
+}
+
+// ---- validate the view, then plan (prove_plan.h): every size and offset of
+// the sections below, no device call
+sezkp_ctx::UploadPlans sezkp_ctx::plan_upload(const sezkp_block_view& v, uint64_t row0, uint64_t& nrows,
+                                              bool from_trace) {
+  const uint32_t nblk = v.n_blocks;
+  // step_start must start at 0 and every block's range must be its steps; the
   // rows are then step_start[nblk] (columns.rs:254-257)
   try {
     plan_require_start0(v.step_start, nblk);
   } catch (const PlanError& e) {
     throw Err{SEZKP_E_INVALID, e.msg};
   }
-  for (uint32_t k = 0; k < nblk && !tv; k++) {
-    if (v.step_hi[k] < v.step_lo[k] || v.step_hi[k] - v.step_lo[k] >= (1ULL << 28))
+  for (uint32_t k = 0; k < nblk && !from_trace; k++) {
+    const StepRange r = check_step_range(v, k);
+    if (r == StepRange::empty_or_long)
       throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step range [" + std::to_string(v.step_lo[k]) +
                                      ", " + std::to_string(v.step_hi[k]) + "] is empty or longer than 2^28"};
-    const uint64_t len = v.step_hi[k] - v.step_lo[k] + 1;
-    const uint64_t steps = v.step_start[k + 1] - v.step_start[k];
-    if (len != steps)
-      throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step_hi-step_lo+1=" + std::to_string(len) +
-                                     " but movement_log has " + std::to_string(steps) + " steps"};
+    if (r == StepRange::other_length)
+      throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step_hi-step_lo+1=" +
+                                     std::to_string(v.step_hi[k] - v.step_lo[k] + 1) + " but movement_log has " +
+                                     std::to_string(v.step_start[k + 1] - v.step_start[k]) + " steps"};
   }
-  // ---- plan (prove_plan.h): every size and offset below, no device call
-  ShapePlan sp;
-  ColumnPlan cp;
-  FriPlan fp;
-  ProofPlan pp;
+  UploadPlans p;
   try {
-    sp = plan_shape(tau, v.step_start, nblk, rank, logP, sharded());
-    cp = plan_columns(sp, v.step_start, getenv("SEZKP_NO_DICT") == nullptr);  // read per upload
-    fp = plan_fri(sp);
-    pp = plan_proof(sp, cp.labels);
+    sp = plan_shape(v.tau, v.step_start, nblk, rank, logP, sharded());
+    p.cp = plan_columns(sp, v.step_start, getenv("SEZKP_NO_DICT") == nullptr);  // read per upload
+    p.fp = plan_fri(sp);
+    p.pp = plan_proof(sp, p.cp.labels);
   } catch (const PlanError& e) {
     throw Err{SEZKP_E_INVALID, e.msg};
   }
-  n = sp.n;
-  if (audit_n != n) free_audit();
-  logn = sp.logn;
-  logN = sp.logN;
-  N = sp.N;
-  ncols = sp.ncols;
-  logChunks = sp.logChunks;
-  ch_lo = sp.ch_lo;
-  ch_hi = sp.ch_hi;
-  blk_lo = sp.blk_lo;
-  blk_cnt = sp.blk_cnt;
-  full_lde = sp.full_lde;
-  M = sp.M;
-  logM = sp.logM;
-  tree_wg_log = sp.tree_wg_log;
-  rR = sp.rR;
+  const uint64_t n = sp.n;
+  if (audit.audit_n != n) audit.release_device();
   if (nrows == ~0ull) nrows = n - row0;
   {  // the rows this context reads: every row (one device) or the whole blocks over its chunks (+ the halo row)
-    const uint64_t need0 = v.step_start[blk_lo], need1 = v.step_start[blk_lo + blk_cnt];
+    const uint64_t need0 = v.step_start[sp.blk_lo], need1 = v.step_start[sp.blk_lo + sp.blk_cnt];
     if (row0 > need0 || row0 + nrows < need1 || row0 + nrows > n)
       throw Err{SEZKP_E_INVALID, "step arrays hold rows [" + std::to_string(row0) + ", " + std::to_string(row0 + nrows) +
                                      ") but this context needs rows [" + std::to_string(need0) + ", " +
                                      std::to_string(need1) + ")"};
   }
+  return p;
+}
 
-  // ---- trace image (tape-major): the step arrays go over as the view holds
-  // them (row-major [n][tau]) and are transposed on the device
-  auto up = [&](auto* dst, const auto* src, size_t count) {
-    if (count) HIP_OR_THROW(hipMemcpy(dst, src, count * sizeof(*src), hipMemcpyHostToDevice));
-  };
+// ---- trace image (tape-major): the step arrays go over as the view holds
+// them (row-major [n][tau]) and are transposed on the device
+void sezkp_ctx::upload_trace_image(const sezkp_block_view& v, uint64_t row0, uint64_t nrows,
+                                   const sezkp_trace_view* tv) {
+  const uint64_t n = sp.n;
+  const uint32_t tau = sp.tau, nblk = sp.nblk;
   staged = false;
   active = 0;
   {
@@ -771,31 +877,38 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   up(d_bs, v.step_start, nblk + 1);
   cur_step_start.assign(v.step_start, v.step_start + nblk + 1);
   if (tv) {
-    // the one synchronisation of a trace upload is run_trace_tables' below
+    // the one synchronisation of a trace upload is run_trace_tables' (upload)
     alloc_trace_meta(slot[0]);
     write_trace_steps(slot[0], *tv, st, false);
   } else {
     write_trace(slot[0], v, st, row0, nrows);
     HIP_OR_THROW(hipStreamSynchronize(st));
   }
-  TraceSlot& t0 = slot[0];
   T.n = n;
   T.tau = (int)tau;
   T.nblk = nblk;
-  T.input_mv = t0.imv;
-  T.mv = t0.mv;
-  T.wflag = t0.wf;
-  T.wsym = t0.ws;
+  bind_trace_slot(slot[0]);
   T.blk_start = d_bs;
-  T.blk_winlen = t0.bw;
-  T.blk_offin = t0.bi;
-  T.blk_offout = t0.bo;
   T.row_blk = dalloc<uint32_t>(n);
   T.row_flags = dalloc<uint8_t>(n);
   T.head = dalloc<int32_t>((size_t)tau * n + 2);
   T.head_rng = dalloc<int64_t>(2 * (size_t)tau * nblk + 2);
+}
 
-  // ---- column templates, tables and work lists (ColumnPlan)
+void sezkp_ctx::bind_trace_slot(const TraceSlot& t) {
+  T.input_mv = t.imv;
+  T.mv = t.mv;
+  T.wflag = t.wf;
+  T.wsym = t.ws;
+  T.blk_winlen = t.bw;
+  T.blk_offin = t.bi;
+  T.blk_offout = t.bo;
+}
+
+// ---- column templates, tables and work lists (ColumnPlan)
+void sezkp_ctx::upload_columns(const ColumnPlan& cp) {
+  const uint64_t n = sp.n;
+  const int ncols = sp.ncols;
   labels = cp.labels;
   const std::vector<ColTemplate>& tm = cp.tmpl;
   const std::vector<DictCol>& dcols = cp.dcols;
@@ -806,18 +919,15 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   pw_blk_cols.clear();
   for (int c = 0; c < ncols; c++)
     if (tm[c].kind >= 7) pw_blk_cols.push_back((uint32_t)c);
-  // column roots, then the guard words ([0] this rank's guard, [8 + r] rank
-  // r's guard when sharded): one D2H copy
-  // and behind them the dictionary cache's status words (k_dict_plan) and
-  // one word per column for the piecewise tables' form (k_col_tables)
-  // and the wide head ladder's status words (HW_STAT_WORDS per dictionary column)
-  d_colroots = dalloc<uint32_t>((size_t)ncols * 8 + 16 + (2 + HW_STAT_WORDS) * dcols.size() + ncols);
-  d_err = d_colroots + (size_t)ncols * 8;
-  d_dstatus = d_err + 16;
-  d_pwstat = d_dstatus + 2 * dcols.size();
-  d_hwstat = d_pwstat + ncols;
+  // column roots, then the guard and status words behind them: one D2H copy (StatusLayout)
+  SL = plan_status(ncols, (int)dcols.size());
+  d_colroots = dalloc<uint32_t>(SL.total);
+  d_err = d_colroots + SL.guard;
+  d_dstatus = d_colroots + SL.dict;
+  d_pwstat = d_colroots + SL.pw;
+  d_hwstat = d_colroots + SL.hw;
   T.pw_stat = d_pwstat;
-  HIP_OR_THROW(hipMemset(d_err, 0, 64));
+  HIP_OR_THROW(hipMemset(d_err, 0, GUARD_WORDS * 4));
   HIP_OR_THROW(hipMemset(d_pwstat, 0, (size_t)ncols * 4));
   d_tabs = dalloc<uint32_t>(cp.tab_nodes * 8 + 8);
   n_tab_cols = (int)cp.tab_cols.size();
@@ -835,25 +945,8 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   up(d_dcols, dcols.data(), dcols.size());
   d_dpart = dalloc<int64_t>(2 * dcols.size() * ((n + 4095) / 4096) + 2);
   d_dplans = dalloc<DictPlan>(dcols.size() + 1);
-  if (dcols.size() != dict_cache_cols) {
-    free_dict_cache();
-    dict_epoch++;
-    const size_t nd = dcols.size();
-    const size_t key_bytes = nd * sizeof(DictKey) + DICT_LEVELS * 8, cache_bytes = key_bytes + nd * 4 + 64;
-    HIP_OR_THROW(hipMalloc((void**)&d_dtabs, (nd * DICT_LEVELS * DICT_CAP * 8 + 8) * sizeof(uint32_t)));
-    // (if this one fails, d_dtabs stays allocated with dict_cache_cols unset:
-    // the next upload, or the destructor, frees it through free_dict_cache)
-    HIP_OR_THROW(hipMalloc((void**)&d_dkeys, cache_bytes));
-    HIP_OR_THROW(hipMemset(d_dkeys, 0, cache_bytes));  // epoch 0 and seq 0 are never passed
-    d_dlvl_seq = reinterpret_cast<uint64_t*>(d_dkeys + nd);
-    d_dreuse = reinterpret_cast<uint32_t*>(d_dlvl_seq + DICT_LEVELS);
-    HIP_OR_THROW(hipMalloc((void**)&d_hw, (nd + 1) * sizeof(HeadWideDev)));
-    HIP_OR_THROW(hipMemset(d_hw, 0, (nd + 1) * sizeof(HeadWideDev)));  // epoch 0, build_seq 0: no ladder
-    hw_cols.assign(nd, HeadWideCol{});
-    hw_recs.assign(nd, HeadWideDev{});
-    dict_cache_cols = nd;
-  }
-  hw_stats.clear();
+  if (dcols.size() != dict.cols) dict.resize(dcols.size());
+  dict.hw_stats.clear();
   {  // what dict_entry reads of the columns besides the plan: label block and table slot
     std::vector<uint8_t> shape(dcols.size() * (sizeof(ColTemplate) + sizeof(DictCol)));
     uint8_t* p = shape.data();
@@ -862,10 +955,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
       memcpy(p + sizeof(ColTemplate), &d, sizeof(DictCol));
       p += sizeof(ColTemplate) + sizeof(DictCol);
     }
-    if (shape != dict_shape) {
-      dict_shape.swap(shape);
-      dict_epoch++;
-    }
+    dict.note_shape(shape);
   }
   d_dlev = dalloc<uint32_t>(dcols.size() * (n >> COL_CHUNK_LOG2) * DLEV_NODES * 8 + 8);
   dict_of = cp.dict_of;
@@ -878,12 +968,44 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   n_work = (int)(cp.work.size() / 2);
   d_work = dalloc<uint32_t>(cp.work.size() + 2);
   up(d_work, cp.work.data(), cp.work.size());
-  outer_stride = tree_stored_nodes(logChunks, 0);
+  outer_stride = tree_stored_nodes(sp.logChunks, 0);
   d_outer = dalloc<uint32_t>((size_t)ncols * outer_stride * 8);
+}
 
-  // ---- LDE / FRI workspace (FriPlan): the buffers, then every layer's
-  // values, trees and roots as base + offset
-  const int k = logN;
+namespace {
+void DictTables::resize(size_t nd) {
+  release();
+  epoch++;
+  const size_t key_bytes = nd * sizeof(DictKey) + DICT_LEVELS * 8, cache_bytes = key_bytes + nd * 4 + 64;
+  HIP_OR_THROW(hipMalloc((void**)&d_dtabs, (nd * DICT_LEVELS * DICT_CAP * 8 + 8) * sizeof(uint32_t)));
+  // (if this one fails, d_dtabs stays allocated with `cols` unset: the next
+  // upload, or the context's destructor, frees it through release)
+  HIP_OR_THROW(hipMalloc((void**)&d_dkeys, cache_bytes));
+  HIP_OR_THROW(hipMemset(d_dkeys, 0, cache_bytes));  // epoch 0 and seq 0 are never passed
+  d_dlvl_seq = reinterpret_cast<uint64_t*>(d_dkeys + nd);
+  d_dreuse = reinterpret_cast<uint32_t*>(d_dlvl_seq + DICT_LEVELS);
+  HIP_OR_THROW(hipMalloc((void**)&d_hw, (nd + 1) * sizeof(HeadWideDev)));
+  HIP_OR_THROW(hipMemset(d_hw, 0, (nd + 1) * sizeof(HeadWideDev)));  // epoch 0, build_seq 0: no ladder
+  hw_cols.assign(nd, HeadWideCol{});
+  hw_recs.assign(nd, HeadWideDev{});
+  cols = nd;
+}
+
+void DictTables::note_shape(std::vector<uint8_t>& shape_now) {
+  if (shape_now != shape) {
+    shape.swap(shape_now);
+    epoch++;
+  }
+}
+}  // namespace
+
+// ---- LDE / FRI workspace (FriPlan): the buffers, then every layer's
+// values, trees and roots as base + offset
+void sezkp_ctx::upload_fri_workspace(const FriPlan& fp) {
+  const uint64_t n = sp.n, N = sp.N, M = sp.M;
+  const uint32_t nblk = sp.nblk;
+  const bool full_lde = sp.full_lde;
+  const int k = sp.logN;
   d_base = dalloc<uint64_t>(n);
   Tm.hr = dalloc<uint64_t>(n);
   Tm.sl = dalloc<uint64_t>(n);
@@ -951,6 +1073,12 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     d_jobs = dalloc<UpperJob>(all.size() + 1);
     if (!all.empty()) up(d_jobs, all.data(), all.size());
   }
+}
+
+// ---- the query requests, then the proof image (ProofPlan): the header's
+// bytes, the body's layout
+void sezkp_ctx::upload_proof_image(const ProofPlan& pp) {
+  const int ncols = sp.ncols, k = sp.logN;
   max_fri_req = pp.max_fri_req;
   max_open_req = pp.max_open_req;
   // The query requests (a few KB per proof) live in mapped host memory that
@@ -959,33 +1087,22 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   // tools/ab_req_mapped.sh: host -> proof 7.91 -> 7.97e9, mean of three)
   h_req = hmapped<uint32_t>(max_fri_req * 3 + max_open_req * OPEN_REQ_WORDS);
   d_req = h_req;
-  // ---- proof image (ProofPlan): the header's bytes, the body's layout
   hdr_bytes = pp.hdr_bytes;
   root_pos = pp.root_pos;
   PL = pp.PL;
   PL.base = dalloc<uint32_t>(PL.total / 4 + 2);
   h_proof = halloc<uint8_t>(hdr_bytes + PL.total);
   memcpy(h_proof, pp.header.data(), hdr_bytes);
-  h_small = halloc<uint32_t>((size_t)(ncols + k + 4) * 8 + (2 + HW_STAT_WORDS) * (size_t)n_dict + (size_t)ncols);
+  // the status copy, later the k + 1 FRI roots with the final value behind them
+  h_small = halloc<uint32_t>(std::max(SL.total, (size_t)(k + 4) * 8));
   d_chal = dalloc<DevChal>(1);
   h_chal = halloc<DevChal>(1);
   d_dict_of = dalloc<uint32_t>((size_t)ncols);
   up(d_dict_of, dict_of.data(), dict_of.size());
-  if (tv) {
-    // partition on the device: heads, block tables, metadata, manifest (a
-    // head outside i32 fails here, with the context left without a trace)
-    slot[0].from_trace = true;
-    slot[0].tables_pending = true;
-    HIP_OR_THROW(hipStreamSynchronize(nullptr));  // the memsets above, before the prover stream writes behind them
-    run_trace_tables();
-  }
-  release_spares();
-  loaded = true;
 }
 
-// ---- a trace uploaded as a raw movement log (sezkp_ctx_upload_trace)
 namespace {
-// answered before any device call; the shape errors are plan_shape's
+// ---- a trace uploaded as a raw movement log (sezkp_ctx_upload_trace)
 void check_trace_view(const sezkp_trace_view* tv) {
   if (!tv) throw Err{SEZKP_E_INVALID, "null argument"};
   if (tv->b == 0) throw Err{SEZKP_E_INVALID, "trace view: b (steps per block) must be at least 1"};
@@ -1002,29 +1119,10 @@ void check_trace_view(const sezkp_trace_view* tv) {
     throw Err{SEZKP_E_INVALID, e.msg};
   }
 }
-std::vector<uint64_t> uniform_step_start(uint64_t t, uint64_t b) {
-  const uint64_t nb = trace_nblk(t, b);
-  std::vector<uint64_t> ss((size_t)nb + 1);
-  for (uint64_t k = 0; k <= nb; k++) ss[(size_t)k] = trace_step_start(k, t, b);
-  return ss;
-}
-// where a caller's array lives: a trace produced on the GPU is copied device
-// to device; a pointer the runtime does not know is pageable host memory
-bool on_device(const void* p, int device) {
-  hipPointerAttribute_t a{};
-  if (hipPointerGetAttributes(&a, p) != hipSuccess) {
-    (void)hipGetLastError();  // not an error of ours
-    return false;
-  }
-  if (a.type != hipMemoryTypeDevice) return false;
-  if (a.device != device)
-    throw Err{SEZKP_E_INVALID, "trace view: a step array lives on device " + std::to_string(a.device) +
-                                   ", the context on device " + std::to_string(device)};
-  return true;
-}
 }  // namespace
 
 void sezkp_ctx::alloc_trace_meta(TraceSlot& t) {
+  const uint32_t tau = sp.tau, nblk = sp.nblk;
   if (!ev_root) HIP_OR_THROW(hipEventCreateWithFlags(&ev_root, hipEventDisableTiming));
   if (t.meta) return;
   const size_t nt = (size_t)tau * nblk;
@@ -1045,22 +1143,16 @@ void sezkp_ctx::alloc_trace_meta(TraceSlot& t) {
 }
 
 void sezkp_ctx::write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy) {
-  const size_t cells = (size_t)tau * n;
+  const uint64_t n = sp.n;
+  const size_t cells = (size_t)sp.tau * n;
   wait_copy_stream();
   HIP_OR_THROW(hipEventSynchronize(t.ready));
-  constexpr size_t chunk = (size_t)4 << 20;  // host sources: as write_trace
   auto cp = [&](void* dst, const void* src, size_t bytes) {
     if (!bytes) return;
     // the kind is named once it is known: the copies of pinned host arrays
     // then take the same path as write_trace's
     const bool dev = on_device(src, device);
-    const size_t step = dev ? bytes : chunk;
-    const hipMemcpyKind kind = dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice;
-    for (size_t o = 0; o < bytes;) {
-      const size_t b = std::min(step, bytes - o);
-      HIP_OR_THROW(hipMemcpyAsync((uint8_t*)dst + o, (const uint8_t*)src + o, b, kind, s));
-      o += b;
-    }
+    copy_chunked(dst, src, bytes, dev ? bytes : COPY_CHUNK, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
   };
   cp(t.raw, tv.wsym, cells * 2);
   cp(t.raw + 2 * cells, tv.mv, cells);
@@ -1088,8 +1180,9 @@ void sezkp_ctx::stage_trace(const sezkp_trace_view& tv) {
   if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded: the first trace of a shape goes through upload"};
   if (sharded()) throw Err{SEZKP_E_INVALID, "stage_trace: not on a sharded context"};
   check_trace_view(&tv);
+  const uint32_t nblk = sp.nblk;
   // the shape check of stage(): tau, block count and block boundaries
-  if (tv.tau != tau || trace_nblk(tv.t, tv.b) != nblk)
+  if (tv.tau != sp.tau || trace_nblk(tv.t, tv.b) != nblk)
     throw Err{SEZKP_E_INVALID, "staged trace has another shape (tau / block count): call sezkp_ctx_upload"};
   for (uint64_t k = 0; k <= nblk; k++)
     if (trace_step_start(k, tv.t, tv.b) != cur_step_start[(size_t)k])
@@ -1111,8 +1204,9 @@ void sezkp_ctx::stage_trace(const sezkp_trace_view& tv) {
 // the prover stream: upload_trace, a report on an image whose proof did not
 // get that far, and the proofs of traces of more than 40 tapes (the host
 // hashes their leaves: trace_plan.h). Every other proof of a staged trace runs
-// the same launches inside its own schedule (prove_body, enqueue_A).
+// the same launches inside its own schedule (ProofRun::columns_to_challenges).
 void sezkp_ctx::run_trace_tables() {
+  const uint32_t tau = sp.tau, nblk = sp.nblk;
   TraceSlot& t = slot[active];
   HIP_OR_THROW(hipSetDevice(device));
   HIP_OR_THROW(launch_expand(st, T, 0, nblk, d_err));
@@ -1182,6 +1276,7 @@ sezkp_ctx::TraceSlot& sezkp_ctx::require_trace_image(const char* who) {
 }
 
 void sezkp_ctx::trace_manifest_leaves(uint8_t* out32, uint64_t max_leaves) {
+  const uint32_t nblk = sp.nblk;
   TraceSlot& t = require_trace_image("manifest_leaves");
   if (max_leaves < nblk)
     throw Err{SEZKP_E_INVALID, "manifest_leaves: room for " + std::to_string(max_leaves) + " leaves, the trace has " +
@@ -1192,6 +1287,7 @@ void sezkp_ctx::trace_manifest_leaves(uint8_t* out32, uint64_t max_leaves) {
 }
 
 void sezkp_ctx::trace_manifest_root(int32_t frontier, uint8_t out[32]) {
+  const uint32_t nblk = sp.nblk;
   TraceSlot& t = require_trace_image("manifest_root");
   if (frontier) {  // Frontier (lib.rs:167-208): rare, .jsonl manifests only; from the leaves on the host
     std::vector<uint8_t> lv((size_t)nblk * 32);
@@ -1212,6 +1308,8 @@ void sezkp_ctx::trace_manifest_root(int32_t frontier, uint8_t out[32]) {
 // follow from (t, b), the rest is the device's metadata image; the step
 // arrays from `steps` (host or device memory) or back from the device
 void sezkp_ctx::trace_blocks(const sezkp_trace_view* steps, BlockStore& s) {
+  const uint64_t n = sp.n;
+  const uint32_t tau = sp.tau, nblk = sp.nblk;
   TraceSlot& t = require_trace_image("trace_blocks");
   if (steps) {
     check_trace_view(steps);
@@ -1264,7 +1362,8 @@ void sezkp_ctx::trace_blocks(const sezkp_trace_view* steps, BlockStore& s) {
 }
 
 void sezkp_ctx::alloc_slot(TraceSlot& t) {
-  const size_t cells = (size_t)tau * n, nt = (size_t)tau * nblk;
+  const uint64_t n = sp.n;
+  const size_t cells = (size_t)sp.tau * n, nt = (size_t)sp.tau * sp.nblk;
   t.imv = dalloc<int8_t>(n);
   t.mv = dalloc<int8_t>(cells);
   t.wf = dalloc<uint8_t>(cells);
@@ -1294,6 +1393,8 @@ void sezkp_ctx::wait_copy_stream() {
 
 // the row-major step arrays in t.raw -> the tape-major image, on `s`
 void sezkp_ctx::launch_image(TraceSlot& t, hipStream_t s, uint64_t row0, uint64_t nrows) {
+  const uint64_t n = sp.n;
+  const uint32_t tau = sp.tau;
   const size_t cells = (size_t)tau * n;
   HIP_OR_THROW(launch_trace_image(s, reinterpret_cast<int8_t*>(t.raw + 2 * cells), t.raw + 3 * cells,
                                   reinterpret_cast<uint16_t*>(t.raw), n, tau, t.mv, t.wf, t.ws, row0, row0 + nrows));
@@ -1307,7 +1408,8 @@ void sezkp_ctx::launch_image(TraceSlot& t, hipStream_t s, uint64_t row0, uint64_
 // the transposition is left to take_staged(), on the prover stream).
 void sezkp_ctx::write_trace(TraceSlot& t, const sezkp_block_view& v, hipStream_t s, uint64_t row0, uint64_t nrows,
                             bool staged_copy) {
-  const size_t cells = (size_t)tau * n, nt = (size_t)tau * nblk;
+  const uint32_t tau = sp.tau, nblk = sp.nblk;
+  const size_t cells = (size_t)tau * sp.n, nt = (size_t)tau * nblk;
   t.from_trace = false;
   t.tables_pending = false;
   // the previous copy out of h_tab (an earlier stage into this slot) and the
@@ -1323,17 +1425,8 @@ void sezkp_ctx::write_trace(TraceSlot& t, const sezkp_block_view& v, hipStream_t
       t.h_tab[nt + o] = v.off_in[i];
       t.h_tab[2 * nt + o] = v.off_out[i];
     }
-  // each array in copies of <= 4 MB, so a proof's D2H copy queued on the same
-  // copy engine waits for one chunk, not for the rest of a 67 MB upload
-  // (round 3, tools/ab_upload_chunk.sh: host -> proof 7.89 -> 7.94e9, within
-  // the run-to-run spread)
-  constexpr size_t chunk = (size_t)4 << 20;
   auto cp = [&](void* dst, const void* src, size_t bytes) {
-    for (size_t o = 0; o < bytes;) {
-      const size_t b = std::min(chunk, bytes - o);
-      HIP_OR_THROW(hipMemcpyAsync((uint8_t*)dst + o, (const uint8_t*)src + o, b, hipMemcpyHostToDevice, s));
-      o += b;
-    }
+    copy_chunked(dst, src, bytes, COPY_CHUNK, hipMemcpyHostToDevice, s);
   };
   uint16_t* raw_ws = reinterpret_cast<uint16_t*>(t.raw);
   int8_t* raw_mv = reinterpret_cast<int8_t*>(t.raw + 2 * cells);
@@ -1349,12 +1442,13 @@ void sezkp_ctx::write_trace(TraceSlot& t, const sezkp_block_view& v, hipStream_t
 }
 
 void sezkp_ctx::check_shape_same(const sezkp_block_view& v) const {
-  if (v.tau != tau || v.n_blocks != nblk)
+  const uint32_t nblk = sp.nblk;
+  if (v.tau != sp.tau || v.n_blocks != nblk)
     throw Err{SEZKP_E_INVALID, "staged trace has another shape (tau / block count): call sezkp_ctx_upload"};
   if (nblk && memcmp(v.step_start, cur_step_start.data(), (size_t)(nblk + 1) * 8) != 0)
     throw Err{SEZKP_E_INVALID, "staged trace has other block boundaries: call sezkp_ctx_upload"};
   for (uint32_t k = 0; k < nblk; k++)  // the checks of upload()
-    if (v.step_hi[k] < v.step_lo[k] || v.step_hi[k] - v.step_lo[k] + 1 != v.step_start[k + 1] - v.step_start[k])
+    if (check_step_range(v, k) != StepRange::ok)
       throw Err{SEZKP_E_INVALID, "block " + std::to_string(k) + ": step range does not match its steps"};
 }
 
@@ -1372,7 +1466,7 @@ void sezkp_ctx::stage(const sezkp_block_view& v_in) {
   TraceSlot& t = slot[1 - active];
   if (!t.imv) alloc_slot(t);  // first stage on this workspace: the spare image
   staged = false;             // (re)filling the spare slot
-  write_trace(t, v, stc, 0, n, true);
+  write_trace(t, v, stc, 0, sp.n, true);
   staged = true;
 }
 
@@ -1388,28 +1482,17 @@ void sezkp_ctx::take_staged() {
     root_in_err = false;
     h_root_valid = false;
     TraceSlot& t = slot[active];
-    T.input_mv = t.imv;
-    T.mv = t.mv;
-    T.wflag = t.wf;
-    T.wsym = t.ws;
-    T.blk_winlen = t.bw;
-    T.blk_offin = t.bi;
-    T.blk_offout = t.bo;
+    bind_trace_slot(t);
     // the copies are done (host-side check, nothing queued on the copy
     // stream's hardware queue), then the transposition runs on the prover
     // stream ahead of this proof's kernels
     if (t.image_pending) {
       wait_copy_stream();
-      launch_image(t, st, 0, n);
+      launch_image(t, st, 0, sp.n);
     } else {
       HIP_OR_THROW(hipStreamWaitEvent(st, t.ready, 0));
     }
   }
-}
-
-static std::string head_range_msg(const std::string& who) {
-  return "a block's head position leaves the i32 range" + who +
-         " (block too long for its moves: block length x max |mv| must stay below 2^31)";
 }
 
 // Full-trace AIR audit (sezkp_stark.h; semantics at k_air_audit, trace.hip):
@@ -1430,22 +1513,24 @@ void sezkp_ctx::air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t
       throw Err{SEZKP_E_INVALID, "air_audit: a staged trace is pending (prove first: the audit reads the image the "
                                  "proofs read)"};
   }
+  const uint64_t n = sp.n;
+  const uint32_t tau = sp.tau;
   if (tau > 256) throw Err{SEZKP_E_INVALID, "air_audit takes at most 256 tapes"};
   HIP_OR_THROW(hipSetDevice(device));
   const size_t words = (size_t)((n + 63) / 64), bytes = (size_t)((n + 7) / 8);
-  if (!h_audit) HIP_OR_THROW(hipHostMalloc(&h_audit, (size_t)AUD_WORDS * 8, hipHostMallocDefault));
-  if (!d_audit) {
-    HIP_OR_THROW(hipMalloc(&d_audit, ((size_t)AUD_WORDS + 2 * words) * 8));
-    audit_n = n;
+  if (!audit.h_audit) HIP_OR_THROW(hipHostMalloc(&audit.h_audit, (size_t)AUD_WORDS * 8, hipHostMallocDefault));
+  if (!audit.d_audit) {
+    HIP_OR_THROW(hipMalloc(&audit.d_audit, ((size_t)AUD_WORDS + 2 * words) * 8));
+    audit.audit_n = n;
   }
-  const AirAuditOut O{d_audit, d_audit + AUD_WORDS, d_audit + AUD_WORDS + words};
+  const AirAuditOut O{audit.d_audit, audit.d_audit + AUD_WORDS, audit.d_audit + AUD_WORDS + words};
   // a trace image whose proof did not get as far as its block tables
   if (slot[active].tables_pending) run_trace_tables();
-  HIP_OR_THROW(launch_expand(st, T, 0, nblk, d_err));
+  HIP_OR_THROW(launch_expand(st, T, 0, sp.nblk, d_err));
   HIP_OR_THROW(launch_air_audit(st, T, O, d_err));
   // the counters and the guard word (k_air_audit_first put it beside them): one copy
-  const uint64_t* c = h_audit;
-  HIP_OR_THROW(hipMemcpyAsync(h_audit, d_audit, (size_t)AUD_WORDS * 8, hipMemcpyDeviceToHost, st));
+  const uint64_t* c = audit.h_audit;
+  HIP_OR_THROW(hipMemcpyAsync(audit.h_audit, audit.d_audit, (size_t)AUD_WORDS * 8, hipMemcpyDeviceToHost, st));
   HIP_OR_THROW(hipStreamSynchronize(st));
   const uint32_t guard = (uint32_t)c[AUD_GUARD];
   if (guard) {
@@ -1493,7 +1578,7 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
   using clk = std::chrono::steady_clock;
   auto ms_since = [](clk::time_point t0) { return std::chrono::duration<double, std::milli>(clk::now() - t0).count(); };
   const auto t_call = clk::now();
-  for (auto& v : vfy_ms) v = 0;
+  for (auto& v : vfy.vfy_ms) v = 0;
   HIP_OR_THROW(hipSetDevice(device));
   size_t cap = (size_t)256 << 20;  // proof bytes per slice
   if (const char* e = getenv("SEZKP_VERIFY_CHUNK_BYTES")) {
@@ -1501,7 +1586,7 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
     if (v > 0 && v < cap) cap = (size_t)v;
   }
   constexpr uint64_t MAX_SLICE_JOBS = 1ull << 28;
-  for (auto& e : vev)
+  for (auto& e : vfy.vev)
     if (!e) HIP_OR_THROW(hipEventCreate(&e));
   std::vector<VerifyItem> items;
   std::vector<size_t> place;  // a proof's first byte in the slice's bytes
@@ -1537,7 +1622,7 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
       place.push_back(at);
     }
     if (njobs > 0xFFFFFFFFull) throw Err{SEZKP_E_INVALID, "verify_batch: a proof with more than 2^32 Merkle paths"};
-    vfy_ms[SEZKP_VT_PARSE] += ms_since(t0);
+    vfy.vfy_ms[SEZKP_VT_PARSE] += ms_since(t0);
     const uint32_t* result = nullptr;
     if (ndev) {
       t0 = clk::now();
@@ -1545,36 +1630,36 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
       const size_t jobs_off = roots_off + 32 * nroots;
       const size_t res_off = jobs_off + sizeof(VerifyJobDev) * (size_t)ndev;
       const size_t total = res_off + 4 * (size_t)njobs;
-      if (total > vfy_cap) {
+      if (total > vfy.vfy_cap) {
         HIP_OR_THROW(hipStreamSynchronize(st));
-        if (d_vfy) (void)hipFree(d_vfy);
-        if (h_vfy) (void)hipHostFree(h_vfy);
-        d_vfy = h_vfy = nullptr;
-        vfy_cap = 0;
+        if (vfy.d_vfy) (void)hipFree(vfy.d_vfy);
+        if (vfy.h_vfy) (void)hipHostFree(vfy.h_vfy);
+        vfy.d_vfy = vfy.h_vfy = nullptr;
+        vfy.vfy_cap = 0;
         const size_t want = total + total / 4;
-        HIP_OR_THROW(hipMalloc(&d_vfy, want));
-        HIP_OR_THROW(hipHostMalloc(&h_vfy, want, hipHostMallocDefault));
-        vfy_cap = want;
+        HIP_OR_THROW(hipMalloc(&vfy.d_vfy, want));
+        HIP_OR_THROW(hipHostMalloc(&vfy.h_vfy, want, hipHostMallocDefault));
+        vfy.vfy_cap = want;
       }
-      if (nlabels > n_vlabels) {
+      if (nlabels > vfy.n_vlabels) {
         std::vector<VerifyLabel> tl((size_t)nlabels);
         for (uint64_t l = 0; l < nlabels; l++) verify_label_template(l, tl[(size_t)l]);
         HIP_OR_THROW(hipStreamSynchronize(st));
-        if (d_vlabels) (void)hipFree(d_vlabels);
-        d_vlabels = nullptr;
-        n_vlabels = 0;
-        HIP_OR_THROW(hipMalloc(&d_vlabels, sizeof(VerifyLabel) * tl.size()));
-        HIP_OR_THROW(hipMemcpy(d_vlabels, tl.data(), sizeof(VerifyLabel) * tl.size(), hipMemcpyHostToDevice));
-        n_vlabels = nlabels;
+        if (vfy.d_vlabels) (void)hipFree(vfy.d_vlabels);
+        vfy.d_vlabels = nullptr;
+        vfy.n_vlabels = 0;
+        HIP_OR_THROW(hipMalloc(&vfy.d_vlabels, sizeof(VerifyLabel) * tl.size()));
+        HIP_OR_THROW(hipMemcpy(vfy.d_vlabels, tl.data(), sizeof(VerifyLabel) * tl.size(), hipMemcpyHostToDevice));
+        vfy.n_vlabels = nlabels;
       }
-      VerifyJobDev* hj = reinterpret_cast<VerifyJobDev*>(h_vfy + jobs_off);
+      VerifyJobDev* hj = reinterpret_cast<VerifyJobDev*>(vfy.h_vfy + jobs_off);
       size_t r0 = 0, j0 = 0, d0 = 0;
       for (size_t k = 0; k < items.size(); k++) {
         const VerifyItem& it = items[k];
         if (it.jobs.empty()) continue;
-        memcpy(h_vfy + place[k], it.ref.bytes, it.ref.len);
+        memcpy(vfy.h_vfy + place[k], it.ref.bytes, it.ref.len);
         for (size_t c = 0; c < it.col_roots.size(); c++)
-          memcpy(h_vfy + roots_off + 32 * (r0 + c), it.ref.bytes + it.col_roots[c], 32);
+          memcpy(vfy.h_vfy + roots_off + 32 * (r0 + c), it.ref.bytes + it.col_roots[c], 32);
         for (const VerifyJob& src : it.jobs) {
           const uint32_t out_word = (uint32_t)j0++;
           if (src.tag & VJ_HOST) continue;
@@ -1589,27 +1674,27 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
         }
         r0 += it.col_roots.size();
       }
-      vfy_ms[SEZKP_VT_PACK] += ms_since(t0);
+      vfy.vfy_ms[SEZKP_VT_PACK] += ms_since(t0);
       t0 = clk::now();
-      HIP_OR_THROW(hipEventRecord(vev[0], st));
-      HIP_OR_THROW(hipMemcpyAsync(d_vfy, h_vfy, res_off, hipMemcpyHostToDevice, st));
-      HIP_OR_THROW(hipEventRecord(vev[1], st));
-      HIP_OR_THROW(launch_verify_chains(st, d_vfy, reinterpret_cast<const VerifyJobDev*>(d_vfy + jobs_off),
-                                        d_vfy + roots_off, d_vlabels, (uint32_t)ndev,
-                                        reinterpret_cast<uint32_t*>(d_vfy + res_off)));
-      HIP_OR_THROW(hipEventRecord(vev[2], st));
-      HIP_OR_THROW(hipMemcpyAsync(h_vfy + res_off, d_vfy + res_off, 4 * (size_t)njobs, hipMemcpyDeviceToHost, st));
-      HIP_OR_THROW(hipEventRecord(vev[3], st));
+      HIP_OR_THROW(hipEventRecord(vfy.vev[0], st));
+      HIP_OR_THROW(hipMemcpyAsync(vfy.d_vfy, vfy.h_vfy, res_off, hipMemcpyHostToDevice, st));
+      HIP_OR_THROW(hipEventRecord(vfy.vev[1], st));
+      HIP_OR_THROW(launch_verify_chains(st, vfy.d_vfy, reinterpret_cast<const VerifyJobDev*>(vfy.d_vfy + jobs_off),
+                                        vfy.d_vfy + roots_off, vfy.d_vlabels, (uint32_t)ndev,
+                                        reinterpret_cast<uint32_t*>(vfy.d_vfy + res_off)));
+      HIP_OR_THROW(hipEventRecord(vfy.vev[2], st));
+      HIP_OR_THROW(hipMemcpyAsync(vfy.h_vfy + res_off, vfy.d_vfy + res_off, 4 * (size_t)njobs, hipMemcpyDeviceToHost, st));
+      HIP_OR_THROW(hipEventRecord(vfy.vev[3], st));
       HIP_OR_THROW(hipStreamSynchronize(st));
-      vfy_ms[SEZKP_VT_DEVICE_WALL] += ms_since(t0);
+      vfy.vfy_ms[SEZKP_VT_DEVICE_WALL] += ms_since(t0);
       float f = 0;
-      HIP_OR_THROW(hipEventElapsedTime(&f, vev[0], vev[1]));
-      vfy_ms[SEZKP_VT_H2D] += f;
-      HIP_OR_THROW(hipEventElapsedTime(&f, vev[1], vev[2]));
-      vfy_ms[SEZKP_VT_KERNEL] += f;
-      HIP_OR_THROW(hipEventElapsedTime(&f, vev[2], vev[3]));
-      vfy_ms[SEZKP_VT_D2H] += f;
-      result = reinterpret_cast<const uint32_t*>(h_vfy + res_off);
+      HIP_OR_THROW(hipEventElapsedTime(&f, vfy.vev[0], vfy.vev[1]));
+      vfy.vfy_ms[SEZKP_VT_H2D] += f;
+      HIP_OR_THROW(hipEventElapsedTime(&f, vfy.vev[1], vfy.vev[2]));
+      vfy.vfy_ms[SEZKP_VT_KERNEL] += f;
+      HIP_OR_THROW(hipEventElapsedTime(&f, vfy.vev[2], vfy.vev[3]));
+      vfy.vfy_ms[SEZKP_VT_D2H] += f;
+      result = reinterpret_cast<const uint32_t*>(vfy.h_vfy + res_off);
     }
     t0 = clk::now();
     size_t j0 = 0;
@@ -1622,12 +1707,12 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
       o.pad = 0;
       snprintf(o.msg, sizeof o.msg, "%s", it.code == SEZKP_OK ? "" : it.msg.c_str());
     }
-    vfy_ms[SEZKP_VT_DECIDE] += ms_since(t0);
-    vfy_ms[SEZKP_VT_JOBS] += (double)njobs;
-    vfy_ms[SEZKP_VT_SLICES] += 1;
+    vfy.vfy_ms[SEZKP_VT_DECIDE] += ms_since(t0);
+    vfy.vfy_ms[SEZKP_VT_JOBS] += (double)njobs;
+    vfy.vfy_ms[SEZKP_VT_SLICES] += 1;
     i = j;
   }
-  vfy_ms[SEZKP_VT_WALL] = ms_since(t_call);
+  vfy.vfy_ms[SEZKP_VT_WALL] = ms_since(t_call);
 }
 
 // The knobs of a proof, read from the environment in this one place. Each
@@ -1644,7 +1729,7 @@ void sezkp_ctx::verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_ve
 struct ProveOptions {
   bool host_trace = false;   // SEZKP_HOST_TRACE=1: host-side marks printed per proof
   bool sync_debug = false;   // SEZKP_SYNC_DEBUG: sync after every launch, to name the failing kernel
-  const char* stall_after = nullptr;  // SEZKP_DEBUG_STALL_AFTER=<rank>:<collective> (prove_body, coll)
+  const char* stall_after = nullptr;  // SEZKP_DEBUG_STALL_AFTER=<rank>:<collective> (ProofRun::coll)
   bool kernel_events = false;  // SEZKP_KERNEL_EVENTS=1: an event pair around the FRI forest launch
   // Per-stage timed events only on request (SEZKP_STAGE_EVENTS=1, or with the
   // kernel events): each timed event record costs the stream ~3.5 us, so the
@@ -1719,183 +1804,43 @@ struct ProveOptions {
   }
 };
 
-size_t sezkp_ctx::prove(const uint8_t mroot[32]) {
-  if (broken)
-    throw Err{SEZKP_E_DEVICE, "context unusable: an earlier prove aborted the communicator after a failure past "
-                              "its first collective, or could not clear a tripped guard word (destroy the context "
-                              "and create a new one)"};
-  coll_issued = false;
-  coll_used = 0;
-  coll_stats.clear();
-  try {
-    return prove_body(mroot);
-  } catch (...) {
-    // peers may already be waiting in a collective this rank will never join
-    // (or this rank in one they never join): abort so that every rank's
-    // enqueued collectives stop and every rank returns an error
-    if (sharded() && coll_issued) {
-      // the stall test hook models a collective stuck on a dead peer; RCCL's
-      // abort makes such a kernel exit, so the hook's wait ends here too
-      // (ncclCommAbort would otherwise wait behind a stream nothing releases)
-      if (stall_word) __atomic_store_n(stall_word, 1u, __ATOMIC_SEQ_CST);
-      comm->abort();
-      broken = true;
-    }
-    throw;
-  }
-}
 
-size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
-  if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded"};
-  have_plans = false;
-  // the trace image was fixed by take_staged() in the public entry point that
-  // started this proof (for prove_async: before the worker runs, so a stage()
-  // issued right after prove_async fills the other slot, never this one)
-  using clk = std::chrono::steady_clock;
-  const auto t_enter = clk::now();
-  double t_sync = 0, t_last = 0;
-  const ProveOptions opt = ProveOptions::read();
-  // host-side marks (us from entry) printed per proof, to split the
-  // Fiat-Shamir round trips into wake-up, host work and launch
-  const bool htrace = opt.host_trace;
-  std::vector<std::pair<const char*, double>> hmarks;
-  auto mark = [&](const char* what) {
-    if (htrace) hmarks.push_back({what, std::chrono::duration<double, std::micro>(clk::now() - t_enter).count()});
-  };
-  auto sync = [&]() {
-    const auto t0 = clk::now();
-    if (sharded() && coll_issued) {
-      try {
-        comm->wait(st, coll_timeout_s());
-      } catch (const std::exception& e) {
-        throw Err{SEZKP_E_DEVICE, std::string("rank ") + std::to_string(rank) + ": " + e.what()};
-      }
-    } else {
-      // (polling hipStreamQuery instead measured 10-20 us slower per proof)
-      HIP_OR_THROW(hipStreamSynchronize(st));
-    }
-    t_last = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
-    t_sync += t_last;
-  };
-  HIP_OR_THROW(hipSetDevice(device));
-  // ---- a trace image (upload_trace / stage_trace). mroot == null
-  // (SEZKP_FLAG_ROOT_FROM_TRACE): the image's own manifest root, which the
-  // side stream leaves behind the guard words, so it comes home with the
-  // column roots. A staged trace is partitioned once, by the proof that takes
-  // it: k_block_tables after k_expand, the manifest kernels on the side
-  // stream. More than 40 tapes: the host hashes the leaves, a round trip of
-  // its own (trace_plan.h).
-  TraceSlot& img = slot[active];
-  const bool root_dev = mroot == nullptr;
-  if (root_dev && !img.from_trace)
-    throw Err{SEZKP_E_INVALID, "manifest root from the trace: the active trace image was uploaded as blocks"};
-  if (img.tables_pending && !manifest_leaf_on_device(tau)) run_trace_tables();
-  const bool trace_tables = img.tables_pending;
-  uint8_t root_home[32];
-  const int k = logN;
-  const bool kprobe = opt.kernel_events, stage_ev = opt.stage_events;
-  auto rec = [&](int s) {
-    if (stage_ev) HIP_OR_THROW(hipEventRecord(ev[s], st));
-  };
-  bool kdone = false;
-  auto krec = [&](bool end) {
-    if (!kprobe) return;
-    HIP_OR_THROW(hipEventRecord(kev[end ? 1 : 0], st));
-    if (end) kdone = true;
-  };
-  auto ok = [&](hipError_t e, const char* what) {
-    if (e == hipSuccess && opt.sync_debug) e = hipStreamSynchronize(st);
-    if (e != hipSuccess) throw Err{SEZKP_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e)};
-  };
-  // "record on A, wait on B": stream `to` goes on after what `from` holds now
-  auto fork = [&](hipStream_t from, hipStream_t to, hipEvent_t e) {
-    HIP_OR_THROW(hipEventRecord(e, from));
-    HIP_OR_THROW(hipStreamWaitEvent(to, e, 0));
-  };
-
-  const bool sharded = this->sharded();
-  const uint64_t S = 1ULL << L16_LOG;
-  // every collective goes through coll(): the failure hook, the events of the
-  // per-collective stats, and the mark that a failure from here on must abort
-  // the communicator. `wire` = bytes this rank sends over the links.
-  auto coll = [&](const char* name, uint64_t wire, auto&& issue) {
-    fail_point(rank, name);
-    while (coll_ev.size() < 2 * (coll_used + 1)) {
-      hipEvent_t e;
-      HIP_OR_THROW(hipEventCreate(&e));
-      coll_ev.push_back(e);
-    }
-    hipEvent_t a = coll_ev[2 * coll_used], b = coll_ev[2 * coll_used + 1];
-    coll_used++;
-    HIP_OR_THROW(hipEventRecord(a, st));
-    coll_issued = true;
-    try {
-      issue();
-    } catch (const Err&) {
-      throw;
-    } catch (const std::exception& e) {
-      throw Err{SEZKP_E_DEVICE, std::string(name) + ": " + e.what()};
-    }
-    HIP_OR_THROW(hipEventRecord(b, st));
-    coll_stats.push_back(CollStat{name, wire, a, b});
-    // test hook: SEZKP_DEBUG_STALL_AFTER=<rank>:<collective> holds that rank's
-    // stream after the collective (a wait on a mapped word released only at
-    // destroy), so the next wait must give up at SEZKP_COLL_TIMEOUT_S
-    if (hook_match(opt.stall_after, rank, name)) {
-      if (!stall_word) {
-        HIP_OR_THROW(hipHostMalloc(&stall_word, 64, hipHostMallocMapped | hipHostMallocCoherent));
-        *stall_word = 0;
-      }
-      HIP_OR_THROW(hipStreamWaitValue32(st, stall_word, 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
-    }
-  };
-  const uint64_t P1 = (uint64_t)world - 1;
-  const uint64_t row_lo = n >= 1024 ? ch_lo << COL_CHUNK_LOG2 : 0;
-  const uint64_t row_hi = n >= 1024 ? ch_hi << COL_CHUNK_LOG2 : n;
-  const bool no_deep_poly = opt.no_deep_poly;
-  const uint32_t dict_tab_cap = opt.dict_tab_cap;
-  const uint64_t dict_plan_rows = opt.dict_plan_rows(row_hi - row_lo);
-  // ---- dictionary table reuse (DictCache): the epoch moves with every
-  // host-side input of make_plan and dict_entry (the upload moves it for the
-  // templates, the DictCols and the table buffers), after a proof on this
-  // context that did not reach its end (its table launches may not all have
-  // run), and on every proof with SEZKP_DICT_CACHE=0 (read per prove), so that
-  // every column is rebuilt
-  {
-    const bool cache_off = opt.dict_cache_off;
-    DictHostKey hk;
-    hk.n = n;
-    hk.nrows = row_hi - row_lo;
-    hk.row0 = row_lo;
-    hk.plan_rows = dict_plan_rows;
-    hk.tab_cap = dict_tab_cap;
-    if (cache_off || dict_dirty || !(hk == dict_hkey)) dict_epoch++;
-    dict_hkey = hk;
-    dict_dirty = true;  // until this proof completes
-    dict_seq++;
-  }
-  // ---- wide head ladders (prove_plan.h: head_wide_decide): which head
-  // columns read their ladder in this proof and which build it first, from
-  // what the last completed proof reported. A warm proof changes no record:
-  // no copy, no launch. SEZKP_HEAD_WIDE=0 (read per prove) leaves the state
-  // alone and commits from the 4-row groups.
+namespace {
+// ---- dictionary table reuse (DictCache): the epoch moves with every
+// host-side input of make_plan and dict_entry (the upload moves it for the
+// templates, the DictCols and the table buffers), after a proof on this
+// context that did not reach its end (its table launches may not all have
+// run), and on every proof with SEZKP_DICT_CACHE=0 (read per prove), so that
+// every column is rebuilt.
+// ---- wide head ladders (prove_plan.h: head_wide_decide): which head
+// columns read their ladder in this proof and which build it first, from
+// what the last completed proof reported. A warm proof changes no record:
+// no copy, no launch. SEZKP_HEAD_WIDE=0 (read per prove) leaves the state
+// alone and commits from the 4-row groups.
+DictTables::Use DictTables::begin_proof(const HostKey& hk, const ProveOptions& opt,
+                                        const std::vector<sezkp_dict_plan_info>& info, hipStream_t st,
+                                        uint32_t* d_dstatus, uint32_t* d_hwstat) {
+  const int n_dict = (int)info.size();
+  if (opt.dict_cache_off || dirty || !(hk == hkey)) epoch++;
+  hkey = hk;
+  dirty = true;  // until this proof completes
+  seq++;
+  Use use;
+  use.hw_built.assign((size_t)n_dict, 0);
   const bool hw_on = opt.head_wide && n_dict > 0 && hw_cols.size() == (size_t)n_dict;
-  std::vector<uint64_t> hw_built((size_t)n_dict, 0);
-  uint64_t hw_max_entries = 0;
-  bool hw_build = false;
   if (hw_on) {
     std::vector<HeadWideDecision> dec((size_t)n_dict);
     uint64_t slot = 0;
     int nhead = 0;
     for (int c = 0; c < n_dict; c++) {
-      if (dict_info[(size_t)c].kind != 6) continue;
+      if (info[(size_t)c].kind != 6) continue;
       nhead++;
-      dec[c] = head_wide_decide(hw_cols[c], dict_epoch, opt.head_wide_cap);
-      hw_build = hw_build || dec[c].build;
+      dec[c] = head_wide_decide(hw_cols[c], epoch, opt.head_wide_cap);
+      use.hw_build = use.hw_build || dec[c].build;
       if (dec[c].use) slot = std::max(slot, dec[c].l3_entries + dec[c].low_entries);
     }
     slot = (slot + 4095) & ~(uint64_t)4095;
-    if (hw_build && slot > hwtabs_nodes) {
+    if (use.hw_build && slot > hwtabs_nodes) {
       // a larger slot per head column: every ladder in place moves, so it is rebuilt
       if (d_hwtabs) {
         HIP_OR_THROW(hipStreamSynchronize(st));
@@ -1910,16 +1855,16 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     bool changed = false;
     int h = 0;
     for (int c = 0; c < n_dict; c++) {
-      if (dict_info[(size_t)c].kind != 6) continue;
+      if (info[(size_t)c].kind != 6) continue;
       const HeadWideCol& hc = hw_cols[c];
       HeadWideDev want = hw_recs[c];
       if (!dec[c].use) {
         want = HeadWideDev{};
       } else if (dec[c].build) {
-        want = HeadWideDev{hc.olo, hc.dmin, hc.span, hc.dR, dict_epoch, dict_seq, (uint64_t)h * hwtabs_nodes,
+        want = HeadWideDev{hc.olo, hc.dmin, hc.span, hc.dR, epoch, seq, (uint64_t)h * hwtabs_nodes,
                            (uint64_t)h * hwtabs_nodes + dec[c].l3_entries};
-        hw_built[c] = dec[c].l3_entries + dec[c].low_entries;
-        hw_max_entries = std::max(hw_max_entries, dec[c].l3_entries);
+        use.hw_built[c] = dec[c].l3_entries + dec[c].low_entries;
+        use.hw_max_entries = std::max(use.hw_max_entries, dec[c].l3_entries);
       }
       if (memcmp(&want, &hw_recs[c], sizeof want) != 0) {
         hw_recs[c] = want;
@@ -1930,55 +1875,87 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     if (changed)
       HIP_OR_THROW(hipMemcpyAsync(d_hw, hw_recs.data(), hw_recs.size() * sizeof(HeadWideDev), hipMemcpyHostToDevice, st));
   }
-  DictCache dcache{d_dkeys, d_dreuse, d_dlvl_seq, d_dstatus, dict_epoch, dict_seq};
-  dcache.hwstat = d_hwstat;
+  use.dcache = DictCache{d_dkeys, d_dreuse, d_dlvl_seq, d_dstatus, epoch, seq};
+  use.dcache.hwstat = d_hwstat;
   if (hw_on && d_hwtabs) {
-    dcache.hw = d_hw;
-    dcache.hwtabs = d_hwtabs;
+    use.dcache.hw = d_hw;
+    use.dcache.hwtabs = d_hwtabs;
   }
-  // (One launch of a workgroup per column instead of the five flat launches,
-  // chosen by the host when the last proof rebuilt nothing, was measured:
-  // 5.3 against 24.6 us for a warm proof, but 138 against 38 us with the head
-  // columns rebuilding and 317 against 104 us for a full rebuild, and a wrong
-  // guess at every change of trace: not kept, profiles/dict_cache/README.md.)
-  uint32_t st_rebuilt = 0, st_pw_by_value = 0;
-  uint64_t st_entries = 0, st_pw_units = 0;
-  const int nguard = sharded ? comm->world : 1;
-  auto check_guards = [&](const uint32_t* g_h, int ng) {
-    for (int r = 0; r < ng; r++) {
-      const uint32_t g = g_h[r];
-      // the guard carries a data-dependent flag (GUARD_HEAD_RANGE from
-      // k_expand): clear it, stream-ordered, so one bad trace does not fail
-      // the later proofs of good ones on this context
-      if (g) {
-        // a failed clear would leave the guard set and fail every later proof
-        // with this one's error: mark the context unusable instead
-        root_in_err = false;  // (the clear takes the trace image's manifest root with it)
-        const hipError_t me = hipMemsetAsync(d_err, 0, 64, st);
-        if (me != hipSuccess) {
-          broken = true;
-          throw Err{SEZKP_E_DEVICE, std::string("guard word tripped (code ") + std::to_string(g) +
-                                        ") and clearing it failed: " + hipGetErrorString(me) +
-                                        "; the context is unusable"};
-        }
-      }
-      const std::string who = " on rank " + std::to_string(sharded ? r : rank);
-      if (g & GUARD_HEAD_RANGE) throw Err{SEZKP_E_INVALID, head_range_msg(who)};
-      if (g) throw Err{SEZKP_E_DEVICE, "column commitment guard tripped" + who + " (code " + std::to_string(g) + ")"};
-    }
-  };
-  // ---- transcript prelude + column roots (prover.rs:67-81) -> alphas,
-  // masks, z: the roots come back and the host's transcript writes the
-  // challenge record that the kernels read. (A device transcript that
-  // derived every challenge on the stream was built in round 4 and measured
-  // slower: one workgroup's chain of dependent BLAKE3 compressions took
-  // 40 / 23 / 54 us per point against ~25 / 17 / 21 us of host round trip; it
-  // was removed in round 5.)
-  Transcript tr("sezkp-stark/v1");
-  const uint64_t shift_inv = hgl_inv(3);
+  return use;
+}
+
+void DictTables::end_proof(const Use& use, const std::vector<sezkp_dict_plan_info>& info,
+                           const std::vector<HeadWideObs>& obs, uint32_t rebuilt, uint64_t entries) {
+  const int n_dict = (int)info.size();
+  dirty = false;  // every table launch of this proof ran: its keys may validate
+  stat_rebuilt = rebuilt;
+  stat_reused = (uint32_t)n_dict - rebuilt;
+  stat_entries = entries;
+  // the wide head ladders: what this proof saw feeds the next proof's decision
+  hw_stats.clear();
+  for (int c = 0; c < n_dict && hw_cols.size() == (size_t)n_dict; c++) {
+    if (info[(size_t)c].kind != 6) continue;
+    head_wide_observe(hw_cols[c], epoch, obs[c]);
+    const HeadWideDev& r = hw_recs[c];
+    const bool in_place = r.epoch == epoch && r.span != 0;
+    sezkp_head_wide_info s{};
+    s.col = info[(size_t)c].col;
+    s.tape = info[(size_t)c].tape;
+    s.origin = in_place ? r.olo : 0;
+    s.span = in_place ? r.span : 0;
+    s.dR = in_place ? r.dR : 0;
+    s.R = obs[c].hi >= obs[c].lo ? (uint64_t)(obs[c].hi - obs[c].lo) + 1 : 0;
+    s.entries_built = use.hw_built[c];
+    s.groups_wide = obs[c].wide;
+    s.groups_fallback = (uint64_t)obs[c].fb_start + obs[c].fb_span;
+    s.groups_out_of_span = obs[c].fb_span;
+    s.table_bytes = in_place ? hwtabs_nodes * 32 : 0;
+    hw_stats.push_back(s);
+  }
+}
+
+using clk = std::chrono::steady_clock;
+
+// The proof as four device phases and three host phases (the Fiat-Shamir
+// round trips). Each device phase issues its work on the streams and ends in
+// a small D2H copy; after the sync the host reads it, runs the transcript
+// (proof_host.h) and fills what the next phase copies in. (Round 6 measured
+// the phases enqueued ahead behind stream wait-value gates that the host
+// opened: a P = 8 rank's device stages took 0.94 against 0.90 ms, the
+// kernels after each gate running slower; the round trips stay
+// synchronous.) One object per proof, on the proving thread's stack.
+struct ProofRun {
+  // host-side marks (us from entry) printed per proof, to split the
+  // Fiat-Shamir round trips into wake-up, host work and launch
+  const clk::time_point t_enter = clk::now();
+  std::vector<std::pair<const char*, double>> hmarks;
+  double t_sync = 0, t_last = 0;
+  sezkp_ctx& c;
+  const ShapePlan& sp;
+  const ProveOptions opt;
+  const hipStream_t st, st2;
+  const bool sharded;
+  const int k;  // log2(N)
+  const uint64_t P1;
+  // the rows this device commits (the rank's chunks)
+  const uint64_t row_lo, row_hi;
+  const uint64_t dict_plan_rows;
+  // ---- a trace image (upload_trace / stage_trace). mroot == null
+  // (SEZKP_FLAG_ROOT_FROM_TRACE): the image's own manifest root, which the
+  // side stream leaves behind the guard words, so it comes home with the
+  // column roots. A staged trace is partitioned once, by the proof that takes
+  // it: k_block_tables after k_expand, the manifest kernels on the side
+  // stream. More than 40 tapes: the host hashes the leaves, a round trip of
+  // its own (trace_plan.h).
+  sezkp_ctx::TraceSlot& img;
+  const uint8_t* mroot;
+  const bool root_dev;
+  bool trace_tables = false;
+  uint8_t root_home[32];
+  // ---- per-proof state
+  Transcript tr{"sezkp-stark/v1"};
   uint64_t z = 0, zn = 0;
   bool dq = false;
-  const size_t gofs = sharded ? 8 : 0;
   // sharded: each rank turns its own rows into D_j (DeepPoly) and one
   // allgather (with the partial sums of f(z)) gives every rank the n values
   // for the n-point INTT its coset needs; without the quotient the
@@ -1991,121 +1968,261 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
   // distributed}_detail.json: two
   // collectives fewer outweigh (P - 1)/P of a 2^21-point INTT; P = 8 1.204
   // -> 1.132 ms predicted), so it is the default.
-  const bool dist_intt = sharded && world > 1 && opt.dist_intt;
-  DeepPoly dpoly{d_dq_rlo, d_dq_rhi, d_dq_rhk};
-  std::vector<uint8_t> roots((size_t)(k + 1) * 32);
+  const bool dist_intt;
+  DeepPoly dpoly;
+  std::vector<uint8_t> roots;
   uint64_t rows[NUM_QUERIES], frows[NUM_QUERIES];
-  std::vector<uint64_t> pos((size_t)NUM_QUERIES * (k + 1));
+  std::vector<uint64_t> pos;
   size_t nf = 0, no = 0;
+  DictTables::Use du;
+  std::vector<HeadWideObs> hw_obs;
+  uint32_t st_rebuilt = 0, st_pw_by_value = 0;
+  uint64_t st_entries = 0, st_pw_units = 0;
+  bool kdone = false;
 
-  // ---- the proof as four device phases and three host phases (the
-  // Fiat-Shamir round trips). Each enqueue_* issues one phase's work on the
-  // streams; each host_* reads what the previous phase copied back, runs the
-  // transcript and fills what the next phase copies in. (Round 6 measured
-  // the phases enqueued ahead behind stream wait-value gates that the host
-  // opened: a P = 8 rank's device stages took 0.94 against 0.90 ms, the
-  // kernels after each gate running slower; the round trips stay
-  // synchronous.)
-  auto enqueue_A = [&]() {
+  // the trace image was fixed by take_staged() in the public entry point that
+  // started this proof (for prove_async: before the worker runs, so a stage()
+  // issued right after prove_async fills the other slot, never this one)
+  ProofRun(sezkp_ctx& ctx, const uint8_t* manifest_root)
+      : c(ctx),
+        sp(ctx.sp),
+        opt(ProveOptions::read()),
+        st(ctx.st),
+        st2(ctx.st2),
+        sharded(ctx.sharded()),
+        k(ctx.sp.logN),
+        P1((uint64_t)ctx.world - 1),
+        row_lo(ctx.sp.n >= 1024 ? ctx.sp.ch_lo << COL_CHUNK_LOG2 : 0),
+        row_hi(ctx.sp.n >= 1024 ? ctx.sp.ch_hi << COL_CHUNK_LOG2 : ctx.sp.n),
+        dict_plan_rows(opt.dict_plan_rows(row_hi - row_lo)),
+        img(ctx.slot[ctx.active]),
+        mroot(manifest_root),
+        root_dev(manifest_root == nullptr),
+        dist_intt(sharded && ctx.world > 1 && opt.dist_intt),
+        dpoly{ctx.d_dq_rlo, ctx.d_dq_rhi, ctx.d_dq_rhk},
+        roots((size_t)(k + 1) * 32),
+        pos((size_t)NUM_QUERIES * (k + 1)),
+        hw_obs((size_t)ctx.n_dict) {}
+
+  void mark(const char* what) {
+    if (opt.host_trace)
+      hmarks.push_back({what, std::chrono::duration<double, std::micro>(clk::now() - t_enter).count()});
+  }
+  void sync() {
+    const auto t0 = clk::now();
+    if (sharded && c.coll_issued) {
+      try {
+        c.comm->wait(st, coll_timeout_s());
+      } catch (const std::exception& e) {
+        throw Err{SEZKP_E_DEVICE, std::string("rank ") + std::to_string(c.rank) + ": " + e.what()};
+      }
+    } else {
+      // (polling hipStreamQuery instead measured 10-20 us slower per proof)
+      HIP_OR_THROW(hipStreamSynchronize(st));
+    }
+    t_last = std::chrono::duration<double, std::milli>(clk::now() - t0).count();
+    t_sync += t_last;
+  }
+  void rec(int s) {
+    if (opt.stage_events) HIP_OR_THROW(hipEventRecord(c.ev[s], st));
+  }
+  void krec(bool end) {
+    if (!opt.kernel_events) return;
+    HIP_OR_THROW(hipEventRecord(c.kev[end ? 1 : 0], st));
+    if (end) kdone = true;
+  }
+  void ok(hipError_t e, const char* what) {
+    if (e == hipSuccess && opt.sync_debug) e = hipStreamSynchronize(st);
+    if (e != hipSuccess) throw Err{SEZKP_E_DEVICE, std::string(what) + ": " + hipGetErrorString(e)};
+  }
+  // "record on A, wait on B": stream `to` goes on after what `from` holds now
+  void fork(hipStream_t from, hipStream_t to, hipEvent_t e) {
+    HIP_OR_THROW(hipEventRecord(e, from));
+    HIP_OR_THROW(hipStreamWaitEvent(to, e, 0));
+  }
+  // every collective goes through coll(): the failure hook, the events of the
+  // per-collective stats, and the mark that a failure from here on must abort
+  // the communicator. `wire` = bytes this rank sends over the links.
+  template <class F>
+  void coll(const char* name, uint64_t wire, F&& issue) {
+    fail_point(c.rank, name);
+    while (c.coll_ev.size() < 2 * (c.coll_used + 1)) {
+      hipEvent_t e;
+      HIP_OR_THROW(hipEventCreate(&e));
+      c.coll_ev.push_back(e);
+    }
+    hipEvent_t a = c.coll_ev[2 * c.coll_used], b = c.coll_ev[2 * c.coll_used + 1];
+    c.coll_used++;
+    HIP_OR_THROW(hipEventRecord(a, st));
+    c.coll_issued = true;
+    try {
+      issue();
+    } catch (const Err&) {
+      throw;
+    } catch (const std::exception& e) {
+      throw Err{SEZKP_E_DEVICE, std::string(name) + ": " + e.what()};
+    }
+    HIP_OR_THROW(hipEventRecord(b, st));
+    c.coll_stats.push_back(sezkp_ctx::CollStat{name, wire, a, b});
+    // test hook: SEZKP_DEBUG_STALL_AFTER=<rank>:<collective> holds that rank's
+    // stream after the collective (a wait on a mapped word released only at
+    // destroy), so the next wait must give up at SEZKP_COLL_TIMEOUT_S
+    if (hook_match(opt.stall_after, c.rank, name)) {
+      if (!c.stall_word) {
+        HIP_OR_THROW(hipHostMalloc(&c.stall_word, 64, hipHostMallocMapped | hipHostMallocCoherent));
+        *c.stall_word = 0;
+      }
+      HIP_OR_THROW(hipStreamWaitValue32(st, c.stall_word, 1, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    }
+  }
+  // the trace image's pending tables, then the dictionary epoch and head ladders of this proof
+  void begin() {
+    if (root_dev && !img.from_trace)
+      throw Err{SEZKP_E_INVALID, "manifest root from the trace: the active trace image was uploaded as blocks"};
+    if (img.tables_pending && !manifest_leaf_on_device(sp.tau)) c.run_trace_tables();
+    trace_tables = img.tables_pending;
+    DictTables::HostKey hk;
+    hk.n = sp.n;
+    hk.nrows = row_hi - row_lo;
+    hk.row0 = row_lo;
+    hk.plan_rows = dict_plan_rows;
+    hk.tab_cap = opt.dict_tab_cap;
+    du = c.dict.begin_proof(hk, opt, c.dict_info, st, c.d_dstatus, c.d_hwstat);
+  }
+
+  void check_guards(const uint32_t* g_h, int ng) {
+    for (int r = 0; r < ng; r++) {
+      const uint32_t g = g_h[r];
+      // the guard carries a data-dependent flag (GUARD_HEAD_RANGE from
+      // k_expand): clear it, stream-ordered, so one bad trace does not fail
+      // the later proofs of good ones on this context
+      if (g) {
+        // a failed clear would leave the guard set and fail every later proof
+        // with this one's error: mark the context unusable instead
+        c.root_in_err = false;  // (the clear takes the trace image's manifest root with it)
+        const hipError_t me = hipMemsetAsync(c.d_err, 0, 64, st);
+        if (me != hipSuccess) {
+          c.broken = true;
+          throw Err{SEZKP_E_DEVICE, std::string("guard word tripped (code ") + std::to_string(g) +
+                                        ") and clearing it failed: " + hipGetErrorString(me) +
+                                        "; the context is unusable"};
+        }
+      }
+      const std::string who = " on rank " + std::to_string(sharded ? r : c.rank);
+      if (g & GUARD_HEAD_RANGE) throw Err{SEZKP_E_INVALID, head_range_msg(who)};
+      if (g) throw Err{SEZKP_E_DEVICE, "column commitment guard tripped" + who + " (code " + std::to_string(g) + ")"};
+    }
+  }
+
+  // device: expand, column commitments, outer trees -> column roots + status words
+  void columns_to_challenges() {
+    TraceDev& T = c.T;
+    uint32_t* const d_err = c.d_err;
     rec(0);
     // ---- column commitments (openings.rs:306-398): this rank's chunks, then
     // every rank gathers all chunk roots and builds the outer trees
-    ok(launch_expand(st, T, blk_lo, blk_cnt, d_err), "expand");
+    ok(launch_expand(st, T, sp.blk_lo, sp.blk_cnt, d_err), "expand");
     if (trace_tables) ok(launch_block_tables(st, T, img.tm, img.bw, img.bi, img.bo), "block_tables");
     rec(1);
     // piecewise / table / dense columns on the side stream, concurrent with the
     // (VALU-bound) dictionary columns; disjoint outer-tree leaves. (Starting
     // them later, beside part of the dictionary chain only, or on a CU-masked
     // stream, measured even or slower in round 3.)
-    fork(st, st2, ev_expand);
-    ok(launch_col_tables(st2, T, d_tmpl, d_tab_cols, n_tab_cols, tab_units, d_tabs, blk_lo, blk_cnt), "col_tables");
-    ok(launch_col_commit(st2, T, d_tmpl, d_work, n_work, d_tabs, d_outer, outer_stride), "col_commit");
-    ok(launch_col_commit_pw(st2, T, d_tmpl, d_pw_cols, n_pw_cols, d_pw_chunks, n_pw_chunks, d_tabs, d_outer,
-                            outer_stride, d_err), "col_commit_pw");
+    fork(st, st2, c.ev_expand);
+    ok(launch_col_tables(st2, T, c.d_tmpl, c.d_tab_cols, c.n_tab_cols, c.tab_units, c.d_tabs, sp.blk_lo, sp.blk_cnt),
+       "col_tables");
+    ok(launch_col_commit(st2, T, c.d_tmpl, c.d_work, c.n_work, c.d_tabs, c.d_outer, c.outer_stride), "col_commit");
+    ok(launch_col_commit_pw(st2, T, c.d_tmpl, c.d_pw_cols, c.n_pw_cols, c.d_pw_chunks, c.n_pw_chunks, c.d_tabs,
+                            c.d_outer, c.outer_stride, d_err), "col_commit_pw");
     // the composition's transcript-independent half (the row sums), also
     // beside the dictionary commitments: only its combine with the alphas is
     // left after the transcript's first round trip
-    ok(launch_compose_terms(st2, T, Tm, row_lo, row_hi - row_lo), "compose_terms");
-    HIP_OR_THROW(hipEventRecord(ev_cols, st2));
+    ok(launch_compose_terms(st2, T, c.Tm, row_lo, row_hi - row_lo), "compose_terms");
+    HIP_OR_THROW(hipEventRecord(c.ev_cols, st2));
     // the manifest of a trace image behind the columns: nothing reads the
     // root before the copy of the column roots, so the dictionary commit and
     // the outer trees do not wait for it (ev_root)
     if (trace_tables) {
-      ok(launch_inhead_scan(st2, T.input_mv, img.tm, nblk), "inhead_scan");
-      ok(launch_manifest_leaves(st2, img.tm, tau, nblk), "manifest_leaves");
-      ok(launch_manifest_tree(st2, img.tm, nblk, img.root, d_err + 8), "manifest_tree");
-      HIP_OR_THROW(hipEventRecord(ev_root, st2));
-    } else if (root_dev && !root_in_err) {
+      ok(launch_inhead_scan(st2, T.input_mv, img.tm, sp.nblk), "inhead_scan");
+      ok(launch_manifest_leaves(st2, img.tm, sp.tau, sp.nblk), "manifest_leaves");
+      ok(launch_manifest_tree(st2, img.tm, sp.nblk, img.root, d_err + 8), "manifest_tree");
+      HIP_OR_THROW(hipEventRecord(c.ev_root, st2));
+    } else if (root_dev && !c.root_in_err) {
       // the root was computed by an earlier call and a guard clear took it
       HIP_OR_THROW(hipMemcpyAsync(d_err + 8, img.root, 32, hipMemcpyDeviceToDevice, st2));
-      HIP_OR_THROW(hipEventRecord(ev_root, st2));
+      HIP_OR_THROW(hipEventRecord(c.ev_root, st2));
     }
+    // (One launch of a workgroup per column instead of the five flat launches,
+    // chosen by the host when the last proof rebuilt nothing, was measured:
+    // 5.3 against 24.6 us for a warm proof, but 138 against 38 us with the head
+    // columns rebuilding and 317 against 104 us for a full rebuild, and a wrong
+    // guess at every change of trace: not kept, profiles/dict_cache/README.md.)
     // (the commit of the K <= 2 columns on a third stream beside table levels
     // 3..4 measured slower, round 6: profiles/r06/ab/dict_split_streams_ab.txt)
-    if (hw_build)
-      ok(launch_head_ladder(st, d_tmpl, d_dcols, n_dict, d_hw, dict_seq, d_hwtabs, hw_max_entries), "head_ladder");
-    ok(launch_dict_commit(st, T, d_tmpl, d_dcols, n_dict, d_dpart, d_dplans, d_dtabs, d_outer, outer_stride, row_lo,
-                          row_hi - row_lo, d_dlev, dcache, dict_tab_cap, dict_plan_rows),
+    if (du.hw_build)
+      ok(launch_head_ladder(st, c.d_tmpl, c.d_dcols, c.n_dict, c.dict.d_hw, c.dict.seq, c.dict.d_hwtabs,
+                            du.hw_max_entries), "head_ladder");
+    ok(launch_dict_commit(st, T, c.d_tmpl, c.d_dcols, c.n_dict, c.d_dpart, c.d_dplans, c.dict.d_dtabs, c.d_outer,
+                          c.outer_stride, row_lo, row_hi - row_lo, c.d_dlev, du.dcache, opt.dict_tab_cap,
+                          dict_plan_rows),
        "col_commit_dict");
-    HIP_OR_THROW(hipStreamWaitEvent(st, ev_cols, 0));
+    HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_cols, 0));
     // test hook (ProveOptions::trip_guard)
-    if (opt.trip_guard && opt.trip_guard_rank == rank) HIP_OR_THROW(hipMemsetAsync(d_err, 0x7f, 1, st));
+    if (opt.trip_guard && opt.trip_guard_rank == c.rank) HIP_OR_THROW(hipMemsetAsync(d_err, 0x7f, 1, st));
     if (sharded) {
       // the chunk roots of every column and every rank's guard word in one
       // group: sharded ranks see all guard words, so a trip on any rank makes
       // ALL ranks fail at the first check, before the next collective (no rank
       // is left blocked in an RCCL call its peers never reach)
-      const size_t bytes = (size_t)(ch_hi - ch_lo) * 32;
-      coll("col_chunk_roots", P1 * (bytes * ncols + 4), [&] {
-        comm->group_start();
-        for (int c = 0; c < ncols; c++) {
-          uint32_t* lvl0 = d_outer + (size_t)c * outer_stride * 8;
-          comm->allgather(lvl0 + ch_lo * 8, lvl0, bytes, st);
+      const size_t bytes = (size_t)(sp.ch_hi - sp.ch_lo) * 32;
+      coll("col_chunk_roots", P1 * (bytes * sp.ncols + 4), [&] {
+        c.comm->group_start();
+        for (int col = 0; col < sp.ncols; col++) {
+          uint32_t* lvl0 = c.d_outer + (size_t)col * c.outer_stride * 8;
+          c.comm->allgather(lvl0 + sp.ch_lo * 8, lvl0, bytes, st);
         }
-        comm->allgather(d_err, d_err + 8, 4, st);
-        comm->group_end();
+        c.comm->allgather(d_err, d_err + 8, 4, st);
+        c.comm->group_end();
       });
     }
     rec(2);
-    TreeDev outer0{d_outer, d_colroots, logChunks, 0};
-    ok(launch_tree_upper(st, &outer0, ncols, outer_stride, 8, 0), "col_outer");
+    TreeDev outer0{c.d_outer, c.d_colroots, sp.logChunks, 0};
+    ok(launch_tree_upper(st, &outer0, sp.ncols, c.outer_stride, 8, 0), "col_outer");
     rec(3);
-    // one copy: the column roots and the guard words stored right behind them
-    // (d_err = d_colroots + 8 ncols; sharded, every rank's word at d_err + 8),
-    // and the dictionary cache's status words and the piecewise tables'
-    // form words behind the 16 guard words
-    // and the wide head ladder's status words behind those
-    if (trace_tables || (root_dev && !root_in_err)) HIP_OR_THROW(hipStreamWaitEvent(st, ev_root, 0));
-    HIP_OR_THROW(hipMemcpyAsync(h_small, d_colroots,
-                                (size_t)ncols * 32 + 4 * (16 + (2 + HW_STAT_WORDS) * (size_t)n_dict + (size_t)ncols),
-                                hipMemcpyDeviceToHost, st));
-  };
-  std::vector<HeadWideObs> hw_obs((size_t)n_dict);
-  auto host_1 = [&]() {
-    const uint32_t* colroots_h = h_small;
-    check_guards(h_small + 8 * ncols + gofs, nguard);
+    // one copy: the column roots and, right behind them, the guard words
+    // (sharded, every rank's word at d_err + 8) and the status words (StatusLayout)
+    if (trace_tables || (root_dev && !c.root_in_err)) HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_root, 0));
+    HIP_OR_THROW(hipMemcpyAsync(c.h_small, c.d_colroots, c.SL.total * 4, hipMemcpyDeviceToHost, st));
+  }
+
+  // host: guards, status words, alphas / mask / z, the DEEP constants
+  void read_column_challenges() {
+    const StatusLayout& SL = c.SL;
+    const uint32_t* const h_small = c.h_small;
+    const int ncols = sp.ncols, n_dict = c.n_dict;
+    check_guards(h_small + SL.guard + (sharded ? 8 : 0), sharded ? c.comm->world : 1);
     if (trace_tables) img.tables_pending = false;
     if (trace_tables || root_dev) {
-      root_in_err = true;
-      memcpy(h_root, h_small + 8 * ncols + 8, 32);
-      h_root_valid = true;
+      c.root_in_err = true;
+      memcpy(c.h_root, h_small + SL.trace_root, 32);
+      c.h_root_valid = true;
     }
     if (root_dev) {
-      memcpy(root_home, h_root, 32);
+      memcpy(root_home, c.h_root, 32);
       mroot = root_home;
     }
-    for (int c = 0; c < n_dict; c++) {
-      st_rebuilt += h_small[8 * ncols + 16 + 2 * c];
-      st_entries += h_small[8 * ncols + 16 + 2 * c + 1];
+    for (int d = 0; d < n_dict; d++) {
+      st_rebuilt += h_small[SL.dict + 2 * d];
+      st_entries += h_small[SL.dict + 2 * d + 1];
     }
-    for (uint32_t c : pw_blk_cols) {
-      const uint32_t units = h_small[8 * ncols + 16 + 2 * n_dict + c];
+    for (uint32_t col : c.pw_blk_cols) {
+      const uint32_t units = h_small[SL.pw + col];
       st_pw_by_value += units != 0;
       st_pw_units += units;
     }
-    for (int c = 0; c < n_dict; c++) {
-      const uint32_t* w = h_small + 8 * ncols + 16 + 2 * n_dict + ncols + HW_STAT_WORDS * c;
-      HeadWideObs& o = hw_obs[c];
+    for (int d = 0; d < n_dict; d++) {
+      const uint32_t* w = h_small + SL.hw + HW_STAT_WORDS * d;
+      HeadWideObs& o = hw_obs[d];
       o.lo = (int64_t)((uint64_t)w[0] | ((uint64_t)w[1] << 32));
       o.hi = (int64_t)((uint64_t)w[2] | ((uint64_t)w[3] << 32));
       o.mlo = (int32_t)w[4];
@@ -2115,84 +2232,64 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       o.fb_start = w[8];
       o.fb_span = w[9];
     }
-    std::vector<uint8_t> colroots((const uint8_t*)colroots_h, (const uint8_t*)colroots_h + (size_t)ncols * 32);
-    for (int c = 0; c < ncols; c++) memcpy(h_proof + root_pos[c], colroots.data() + 32 * c, 32);
+    const uint8_t* colroots = reinterpret_cast<const uint8_t*>(h_small + SL.roots);
+    for (int col = 0; col < ncols; col++) memcpy(c.h_proof + c.root_pos[col], colroots + 32 * col, 32);
 
-    // ---- transcript prelude + column roots (prover.rs:67-81); every rank
-    // replays the same transcript, so challenges need no broadcast
-    tr.absorb("manifest_root", mroot, 32);
-    tr.absorb_u64("n", n);
-    tr.absorb_u64("tau", tau);
-    tr.absorb_u64("n_cols", (uint64_t)ncols);
-    for (int c = 0; c < ncols; c++) tr.absorb("col_root", colroots.data() + 32 * c, 32);
-    // alphas (params.rs:82-92) with the reuse of prover.rs:86-98
+    // ---- transcript prelude + column roots -> alphas, masks, z: the host's
+    // transcript writes the challenge record that the kernels read. (A device
+    // transcript that derived every challenge on the stream was built in round
+    // 4 and measured slower: one workgroup's chain of dependent BLAKE3
+    // compressions took 40 / 23 / 54 us per point against ~25 / 17 / 21 us of
+    // host round trip; it was removed in round 5.)
+    absorb_column_roots(tr, mroot, sp.n, sp.tau, ncols, colroots);
     mark("tr_roots");
-    auto ab = tr.challenge("alphas", 64);
-    uint64_t a[8];
-    for (int i = 0; i < 8; i++) a[i] = rd64(ab.data() + 8 * i) % GL_P_HOST;
-    // masks (masking.rs:56-79): one cubic
-    tr.absorb("masks", "masks", 5);
-    tr.absorb_u64("n_masks", 1);
-    tr.absorb_u64("deg", 4);
-    uint64_t mask[4];
-    for (int j = 0; j < 4; j++) mask[j] = rd64(tr.challenge("mask_coeff", 8).data()) % GL_P_HOST;
-    // OOD point + coset nudge (prover.rs:119-135)
-    z = rd64(tr.challenge("ood_point", 8).data()) % GL_P_HOST;
-    for (;;) {
-      uint64_t t = hgl_mul(z, shift_inv);
-      for (int i = 0; i < k; i++) t = hgl_mul(t, t);
-      if (t != 1) break;
-      z = hgl_add(z, 1);
-    }
-    for (int i = 0; i < 8; i++) h_chal->alpha[i] = a[i];
-    for (int j = 0; j < 4; j++) h_chal->mask[j] = mask[j];
-    zn = hgl_pow(z, n);
+    const ColumnChallenges ch = column_challenges(tr, sp.n, k);
+    z = ch.z;
+    zn = ch.zn;
+    DevChal* const h_chal = c.h_chal;
+    for (int i = 0; i < 8; i++) h_chal->alpha[i] = ch.alpha[i];
+    for (int j = 0; j < 4; j++) h_chal->mask[j] = ch.mask[j];
     // ---- composition (this rank's rows), DEEP quotient, INTT
     mark("z_done");
     // single device: DEEP as the LDE of H = q + c S (DeepPoly); the base
     // evaluations become q(w^j) before the INTT. Not when z^n = 1 (z on the
     // base domain) or z = 0, nor below 16 rows: the per-point DEEP below.
     mark("compose_issued");
-    dq = logn >= 4 && z != 0 && zn != 1 && !no_deep_poly;
+    dq = sp.logn >= 4 && z != 0 && zn != 1 && !opt.no_deep_poly;
     if (dq) {
-      const uint64_t K1 = hgl_mul(hgl_sub(1, zn), hgl_inv(n % GL_P_HOST));             // f(z) = K1 S
-      const uint64_t zN = hgl_pow(zn, N / n);
-      uint64_t K2 = hgl_mul(hgl_pow(z, N - 1), hgl_inv(hgl_sub(hgl_pow(3, N), zN)));  // c' = f(z) K2
-      // rank g evaluates the coset 3 w_N^g <w_M>: H's N coefficients fold to M
-      // (M >= n): h'_k = [k < n] q_k (3 w_N^g)^k + c' G rho^k, rho = (3/z) w_N^g,
-      // G = sum_{t<P} rho^(tM); single device: rho = 3/z, G = 1
-      // (full_lde: the whole domain, as on one device)
-      const int cP = full_lde ? 0 : logP;
-      const uint64_t cg = full_lde ? 0 : (uint64_t)rank;
-      const uint64_t M_ = N >> cP;
-      const uint64_t rho = hgl_mul(hgl_mul(3, hgl_inv(z)), hgl_pow(hgl_root_2exp((uint32_t)logN), cg));
-      const uint64_t rhoM = hgl_pow(rho, M_);
-      uint64_t G = 0, pw = 1;
-      for (int t = 0; t < (1 << cP); t++) {
-        G = hgl_add(G, pw);
-        pw = hgl_mul(pw, rhoM);
-      }
-      K2 = hgl_mul(K2, G);
+      const DeepConsts d = deep_constants(z, sp.n, sp.N, sp.logN, c.logP, c.rank, sp.full_lde);
       h_chal->z = z;
       h_chal->zn = zn;
-      h_chal->K1 = K1;
-      h_chal->K2 = K2;
-      h_chal->rho = rho;
-      h_chal->rho4096 = hgl_pow(rho, 4096);
-      h_chal->K3 = hgl_mul(hgl_mul(zn, hgl_inv(z)), hgl_inv(n % GL_P_HOST));  // z^(n-1) / n: kappa = K3 S
+      h_chal->K1 = d.K1;
+      h_chal->K2 = d.K2;
+      h_chal->rho = d.rho;
+      h_chal->rho4096 = d.rho4096;
+      h_chal->K3 = d.K3;
     }
-  };
-  auto enqueue_B = [&]() {
+  }
+
+  // device: composition, INTT, coset LDE, layer-0 tree -> its root
+  void lde_layer0_to_betas() {
+    const uint64_t n = sp.n, M = sp.M;
+    const int logn = sp.logn, logN = sp.logN, logP = c.logP, logM = sp.logM, rank = c.rank;
+    const bool full_lde = sp.full_lde;
+    const NttTables& tw = c.tw;
+    DevChal* const d_chal = c.d_chal;
+    uint64_t* const d_base = c.d_base;
+    uint64_t* const d_lde = c.d_lde;
+    uint64_t* const d_cyc = c.d_cyc;
+    uint64_t* const d_dq_part = c.d_dq_part;
+    Comm* const comm = c.comm.get();
     // alphas, masks and the DEEP constants for the kernels below
-    HIP_OR_THROW(hipMemcpyAsync(d_chal, h_chal, offsetof(DevChal, beta), hipMemcpyHostToDevice, st));
+    HIP_OR_THROW(hipMemcpyAsync(d_chal, c.h_chal, offsetof(DevChal, beta), hipMemcpyHostToDevice, st));
     const uint64_t dq_per = dq_rows_per_part(row_hi - row_lo);  // base rows per partial sum (k_inv_base WG)
     if (dq) {
       // the composition's combine (alphas, mask) fused with the DEEP quotient:
       // D_j = C_j / (w^j - z) and the partial sums of f(z) (DeepPoly); the
       // INTT runs on D, f(z) is needed by the tables only
-      ok(launch_inv_base(st, Tm, d_base, d_dq_part, logn, d_chal, tw, row_lo, row_hi - row_lo, dq_per), "inv_base");
+      ok(launch_inv_base(st, c.Tm, d_base, d_dq_part, logn, d_chal, tw, row_lo, row_hi - row_lo, dq_per), "inv_base");
     } else {
-      ok(launch_compose_combine(st, Tm, d_chal, tw, logn, d_base, row_lo, row_hi - row_lo), "compose");
+      ok(launch_compose_combine(st, c.Tm, d_chal, tw, logn, d_base, row_lo, row_hi - row_lo), "compose");
       if (sharded && !dist_intt)
         coll("base_values", P1 * (row_hi - row_lo) * 8,
              [&] { comm->allgather(d_base + row_lo, d_base, (size_t)(row_hi - row_lo) * 8, st); });
@@ -2209,7 +2306,7 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       uint64_t* blk = d_base + row_lo;
       // d_lde: r[g Q + t] = x[g m + rank Q + t]
       coll("intt_alltoall1", P1 * Q * 8, [&] { comm->alltoall(blk, d_lde, Q * 8, st); });
-      ok(bintt_dft_twiddle(st, d_lde, world, Q, (uint32_t)rank, logn, tw), "intt_dft");
+      ok(bintt_dft_twiddle(st, d_lde, c.world, Q, (uint32_t)rank, logn, tw), "intt_dft");
       coll("intt_alltoall2", P1 * Q * 8, [&] { comm->alltoall(d_lde, blk, Q * 8, st); });  // blk[j] = y_rank[j]
       ok(ntt_dif(st, blk, logn - logP, true, tw), "intt_local");  // slot p: n a_(rank + P bitrev(p))
       coll("intt_coeffs", P1 * (m * 8 + (dq ? m / dq_per * 8 : 0)), [&] {
@@ -2232,16 +2329,18 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       // kappa r^(4096t) power tables: a latency-bound ~10 us) on the side
       // stream beside the INTT, which does not read them
       if (dq) {
-        fork(st, st2, ev_qin);
-        ok(launch_q_tables(st2, d_dq_part, logn, full_lde ? logN : logM, d_chal, d_dq_rlo, d_dq_rhi, d_dq_rhk, dq_per),
+        fork(st, st2, c.ev_qin);
+        ok(launch_q_tables(st2, d_dq_part, logn, full_lde ? logN : logM, d_chal, c.d_dq_rlo, c.d_dq_rhi, c.d_dq_rhk,
+                           dq_per),
            "q_tables");
-        HIP_OR_THROW(hipEventRecord(ev_qout, st2));
+        HIP_OR_THROW(hipEventRecord(c.ev_qout, st2));
       }
       ok(ntt_dif(st, d_base, logn, true, tw), "intt");  // -> n * coeffs, bit-reversed
-      if (dq) HIP_OR_THROW(hipStreamWaitEvent(st, ev_qout, 0));
+      if (dq) HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_qout, 0));
     }
     if (dq && dist_intt)
-      ok(launch_q_tables(st, d_dq_part, logn, full_lde ? logN : logM, d_chal, d_dq_rlo, d_dq_rhi, d_dq_rhk, dq_per),
+      ok(launch_q_tables(st, d_dq_part, logn, full_lde ? logN : logM, d_chal, c.d_dq_rlo, c.d_dq_rhi, c.d_dq_rhk,
+                         dq_per),
          "q_tables");
     rec(5);
     // ---- coset LDE (prover.rs:137-189, lde.rs:42-97): rank g evaluates on
@@ -2267,44 +2366,55 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     if (full_lde) {  // this rank's runs of 4096 out of the whole LDE
       ok(launch_runs_extract(st, d_cyc, d_lde, M, logP, (uint32_t)rank), "runs_extract");
     } else if (sharded) {  // cyclic coset -> runs of 4096: one all-to-all over xGMI
-      ok(launch_cyc_pack(st, d_cyc, d_xbuf, M, logP), "cyc_pack");
-      coll("lde_alltoall", P1 * (M >> logP) * 8, [&] { comm->alltoall(d_xbuf, d_cyc, (size_t)(M >> logP) * 8, st); });
+      ok(launch_cyc_pack(st, d_cyc, c.d_xbuf, M, logP), "cyc_pack");
+      coll("lde_alltoall", P1 * (M >> logP) * 8,
+           [&] { comm->alltoall(c.d_xbuf, d_cyc, (size_t)(M >> logP) * 8, st); });
       ok(launch_cyc_unpack(st, d_cyc, d_lde, M, logP), "cyc_unpack");
     }
     rec(7);
     // ---- layer-0 tree: local runs, then the cap from allgathered run roots
-    if (rR >= 0) {
-      ok(launch_layer16(st, d_lde, nullptr, ltrees[0].logLen, 0, 0, ltrees[0], wg_stop(), nullptr, tree_wg_log),
+    const std::vector<TreeDev>& ltrees = c.ltrees;
+    if (sp.rR >= 0) {
+      ok(launch_layer16(st, d_lde, nullptr, ltrees[0].logLen, 0, 0, ltrees[0], sp.wg_stop(), nullptr, sp.tree_wg_log),
          "layer0_tree");
       rec(ST_L0TREE + 1);
-      for (auto& p : jobsL0) ok(launch_upper_jobs(st, d_jobs + p.first, p.second), "layer0_runroots");
+      for (auto& p : c.jobsL0) ok(launch_upper_jobs(st, c.d_jobs + p.first, p.second), "layer0_runroots");
       if (sharded) {
         const uint64_t nrun = M >> L16_LOG;
         const uint32_t* lv12 = ltrees[0].nodes + 8 * tree_level_off(ltrees[0].logLen, LSTORE_FRI, L16_LOG);
-        coll("layer0_run_roots", P1 * nrun * 32, [&] { comm->allgather(lv12, rr_gather[0], (size_t)nrun * 32, st); });
+        coll("layer0_run_roots", P1 * nrun * 32,
+             [&] { comm->allgather(lv12, c.rr_gather[0], (size_t)nrun * 32, st); });
       }
-      for (auto& p : jobs0) ok(launch_upper_jobs(st, d_jobs + p.first, p.second), "layer0_upper");
+      for (auto& p : c.jobs0) ok(launch_upper_jobs(st, c.d_jobs + p.first, p.second), "layer0_upper");
     } else {
       ok(launch_leaf_subtree(st, d_lde, nullptr, logN, 0, 0, ltrees[0]), "layer0_tree");
       rec(ST_L0TREE + 1);
     }
     rec(ST_L0UP + 1);
     // ---- layer-0 root -> all betas at once (prover.rs:184-198)
-    HIP_OR_THROW(hipMemcpyAsync(h_small, d_roots, 32, hipMemcpyDeviceToHost, st));
-  };
-  auto host_2 = [&]() {
-    memcpy(roots.data(), h_small, 32);
-    tr.absorb("fri_layer_root", roots.data(), 32);
-    auto bb = tr.challenge("fri_betas", 8 * (size_t)k);
-    for (int r = 0; r < k; r++) h_chal->beta[r] = rd64(bb.data() + 8 * r) % GL_P_HOST;
-  };
-  auto enqueue_C = [&]() {
-    HIP_OR_THROW(hipMemcpyAsync(d_chal->beta, h_chal->beta, 8 * (size_t)k, hipMemcpyHostToDevice, st));
+    HIP_OR_THROW(hipMemcpyAsync(c.h_small, c.d_roots, 32, hipMemcpyDeviceToHost, st));
+  }
+
+  // host: layer-0 root -> betas
+  void read_betas() {
+    memcpy(roots.data(), c.h_small, 32);
+    fri_betas(tr, roots.data(), k, c.h_chal->beta);
+  }
+
+  // device: folds and layer trees -> FRI roots
+  void fri_to_queries() {
+    const uint64_t N = sp.N;
+    const int rR = sp.rR, logP = c.logP, tail_first = c.tail_first, tree_wg_log = sp.tree_wg_log;
+    const std::vector<uint64_t*>& lvals = c.lvals;
+    const std::vector<TreeDev>& ltrees = c.ltrees;
+    Comm* const comm = c.comm.get();
+    const uint64_t S = 1ULL << L16_LOG;
+    HIP_OR_THROW(hipMemcpyAsync(c.d_chal->beta, c.h_chal->beta, 8 * (size_t)k, hipMemcpyHostToDevice, st));
 
     // ---- FRI folds + layer trees (prover.rs:192-239). Folds of run layers are
     // rank-local (i and i + len/2 share i mod 4096P). The kernels read the
     // betas from the challenge record: beta r folds layer r into layer r + 1.
-    const uint64_t* dbeta = d_chal->beta;
+    const uint64_t* dbeta = c.d_chal->beta;
     // layers of <= 2^11 leaves: one launch on the side stream, overlapping the
     // forest / upper levels (its source is the last fold-chain output)
     auto tail_args = [&](const uint64_t* src_vals) {
@@ -2321,12 +2431,12 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
     auto launch_tail = [&](const uint64_t* src_vals) {
       if (tail_first > k) return;
       const TailArgs ta = tail_args(src_vals);
-      fork(st, st2, ev_fold);
+      fork(st, st2, c.ev_fold);
       ok(launch_fri_tail(st2, ta), "fri_tail");
-      HIP_OR_THROW(hipEventRecord(ev_tail, st2));
+      HIP_OR_THROW(hipEventRecord(c.ev_tail, st2));
     };
     mark("folds");
-    const bool tail_merged = !sharded && tail_first <= k && n_forest > 0 && d_tailbuf;
+    const bool tail_merged = !sharded && tail_first <= k && c.n_forest > 0 && c.d_tailbuf;
     // fold chain, up to FOLD_MAX layers per pass (2 measured even); the forest
     // follows the whole chain (hashing the first pass's layers beside the later
     // folds measured slower in round 3: the forest starves the folds)
@@ -2348,28 +2458,28 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
       }
     };
     fold_chain(lvals[0], 0, rR, "fri_foldm", "fri_fold");
-    const uint64_t* rep_src = rR >= 0 ? lvals[rR] : d_lde;  // full values of the layer above the replicated ones
+    const uint64_t* rep_src = rR >= 0 ? lvals[rR] : c.d_lde;  // full values of the layer above the replicated ones
     // single device: the small layers ride in the forest launch's first
     // workgroups (sharded: their own kernel on the side stream)
     if (tail_merged) {
       const TailArgs ta = tail_args(rep_src);
       krec(false);
-      ok(launch_forest16(st, d_forest, n_forest, forest_wgs, &ta, d_tailbuf, 0, tree_wg_log), "fri_forest");
+      ok(launch_forest16(st, c.d_forest, c.n_forest, c.forest_wgs, &ta, c.d_tailbuf, 0, tree_wg_log), "fri_forest");
       krec(true);
     } else if (!sharded) {
       launch_tail(rep_src);
-      ok(launch_forest16(st, d_forest, n_forest, forest_wgs, nullptr, nullptr, 0, tree_wg_log), "fri_forest");
+      ok(launch_forest16(st, c.d_forest, c.n_forest, c.forest_wgs, nullptr, nullptr, 0, tree_wg_log), "fri_forest");
     } else {
       // the whole of layer rR, then the replicated layers folded from it in one
       // pass, the tail (side stream) and one forest of run + replicated layers
-      coll("fri_rep_values", P1 * S * 8, [&] { comm->allgather(lvals[rR], d_rep, (size_t)S * 8, st); });
-      rep_src = d_rep;
-      fold_chain(d_rep, rR, rR + (int)rep16.size(), "fri_rep_folds", "fri_rep_fold");
-      if (!rep16.empty()) rep_src = lvals[rep16.back()];
+      coll("fri_rep_values", P1 * S * 8, [&] { comm->allgather(lvals[rR], c.d_rep, (size_t)S * 8, st); });
+      rep_src = c.d_rep;
+      fold_chain(c.d_rep, rR, rR + (int)c.rep16.size(), "fri_rep_folds", "fri_rep_fold");
+      if (!c.rep16.empty()) rep_src = lvals[c.rep16.back()];
       // (the tail launched after the forest instead measured even, round 6)
       launch_tail(rep_src);
-      ok(launch_forest16(st, d_forest, n_forest, forest_wgs, nullptr, nullptr, 0, tree_wg_log), "fri_forest");
-      for (auto& p : jobsLR) ok(launch_upper_jobs(st, d_jobs + p.first, p.second), "fri_runroots");
+      ok(launch_forest16(st, c.d_forest, c.n_forest, c.forest_wgs, nullptr, nullptr, 0, tree_wg_log), "fri_forest");
+      for (auto& p : c.jobsLR) ok(launch_upper_jobs(st, c.d_jobs + p.first, p.second), "fri_runroots");
       uint64_t wire = 0;
       for (int r = 1; r <= rR; r++) wire += P1 * ((N >> r) >> (L16_LOG + logP)) * 32;
       coll("fri_run_roots", wire, [&] {
@@ -2377,221 +2487,169 @@ size_t sezkp_ctx::prove_body(const uint8_t mroot[32]) {
         for (int r = 1; r <= rR; r++) {
           const uint64_t nrun = (N >> r) >> (L16_LOG + logP);
           const uint32_t* lv12 = ltrees[r].nodes + 8 * tree_level_off(ltrees[r].logLen, LSTORE_FRI, L16_LOG);
-          comm->allgather(lv12, rr_gather[r], (size_t)nrun * 32, st);
+          comm->allgather(lv12, c.rr_gather[r], (size_t)nrun * 32, st);
         }
         comm->group_end();
       });
       // (the caps' first upper-level pass reads the gathered roots in place)
     }
-    for (auto& p : jobsF) ok(launch_upper_jobs(st, d_jobs + p.first, p.second), "fri_upper");
-    if (tail_first <= k && !tail_merged) HIP_OR_THROW(hipStreamWaitEvent(st, ev_tail, 0));
+    for (auto& p : c.jobsF) ok(launch_upper_jobs(st, c.d_jobs + p.first, p.second), "fri_upper");
+    if (tail_first <= k && !tail_merged) HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_tail, 0));
     rec(ST_FRI + 1);
     // ---- FRI roots -> query rows mod n and mod N (prover.rs:248, 297), the
     // path / opening requests each rank owns
-    if (sharded) HIP_OR_THROW(hipMemsetAsync(PL.base, 0, PL.total, st));  // one writer per byte
-    HIP_OR_THROW(hipMemcpyAsync(h_small, d_roots, (size_t)(k + 1) * 32, hipMemcpyDeviceToHost, st));
-  };
-  auto host_3 = [&]() {
-    memcpy(roots.data(), h_small, (size_t)(k + 1) * 32);
-    for (int r = 1; r <= k; r++) tr.absorb("fri_layer_root", roots.data() + 32 * r, 32);
+    if (sharded) HIP_OR_THROW(hipMemsetAsync(c.PL.base, 0, c.PL.total, st));  // one writer per byte
+    HIP_OR_THROW(hipMemcpyAsync(c.h_small, c.d_roots, (size_t)(k + 1) * 32, hipMemcpyDeviceToHost, st));
+  }
 
+  // host: query rows, this rank's path and opening requests
+  void read_queries() {
+    memcpy(roots.data(), c.h_small, (size_t)(k + 1) * 32);
+    absorb_fri_roots(tr, roots.data(), k);
     // ---- queries (prover.rs:248, 297)
     mark("tr_fri");
-    auto qb = tr.challenge("row_queries", 8 * NUM_QUERIES);
-    for (int i = 0; i < NUM_QUERIES; i++) rows[i] = rd64(qb.data() + 8 * i) % n;
-    auto fb = tr.challenge("row_queries", 8 * NUM_QUERIES);
-    for (int i = 0; i < NUM_QUERIES; i++) frows[i] = rd64(fb.data() + 8 * i) % N;
-
+    query_rows(tr, sp.n, sp.N, rows, frows);
     mark("queries");
-    // FRI path requests (layer, index, ordinal) for the records this rank owns:
-    // run layers by run owner, replicated layers on rank 0
-    for (int q = 0; q < NUM_QUERIES; q++) {
-      uint64_t* p = &pos[(size_t)q * (k + 1)];
-      p[0] = frows[q];
-      uint64_t len = N;
-      for (int r = 0; r < k; r++) {
-        const uint64_t half = len / 2;
-        for (int side = 0; side < 2; side++) {
-          const uint64_t idx = side ? (p[r] ^ half) : p[r];
-          const int owner = (sharded && r <= rR) ? (int)((idx >> L16_LOG) & (uint64_t)(world - 1)) : 0;
-          if (owner != rank) continue;
-          h_req[3 * nf] = (uint32_t)r;
-          h_req[3 * nf + 1] = (uint32_t)idx;
-          h_req[3 * nf + 2] = (uint32_t)(q * 2 * k + 2 * r + side);
-          nf++;
-        }
-        p[r + 1] = p[r] % half;
-        len = half;
-      }
-    }
-    // column opening requests in proof order (prover.rs:252-292, proof.rs:44-66),
-    // each by the rank owning the row's chunk
-    uint32_t* oreq = h_req + 3 * max_fri_req;
-    size_t ord = 0;
-    auto push_open = [&](int c, uint64_t row) {
-      const uint64_t ch = n >= 1024 ? row >> COL_CHUNK_LOG2 : 0;
-      if (ch >= ch_lo && ch < ch_hi) {
-        uint32_t* rq = oreq + (size_t)OPEN_REQ_WORDS * no;
-        rq[0] = (uint32_t)c;
-        rq[1] = (uint32_t)row;
-        rq[2] = (uint32_t)(row >> 32);
-        rq[3] = (uint32_t)ord;
-        rq[4] = dict_of[c];
-        no++;
-      }
-      ord++;
-    };
-    for (int q = 0; q < NUM_QUERIES; q++) {
-      const uint64_t row = rows[q], ip1 = row + 1 < n ? row + 1 : 0;  // next_wrap
-      for (uint32_t r = 0; r < tau; r++) {
-        push_open(3 + 0 * tau + r, row);   // mv
-        push_open(3 + 0 * tau + r, ip1);   // next_mv
-        push_open(3 + 1 * tau + r, row);   // write_flag
-        push_open(3 + 2 * tau + r, row);   // write_sym
-        push_open(3 + 3 * tau + r, row);   // head
-        push_open(3 + 3 * tau + r, ip1);   // next_head
-        push_open(3 + 4 * tau + r, row);   // win_len
-        push_open(3 + 5 * tau + r, row);   // in_off
-        push_open(3 + 6 * tau + r, row);   // out_off
-      }
-      push_open(1, row);  // is_first
-      push_open(2, row);  // is_last
-      push_open(0, row);  // input_mv
-    }
-  };
-  auto enqueue_D = [&](size_t nf_grid, size_t no_grid) {
+    const RequestCounts cnt =
+        plan_requests(sp, c.dict_of.data(), rows, frows, pos.data(), c.h_req, c.h_req + 3 * c.max_fri_req);
+    nf = cnt.nf;
+    no = cnt.no;
+  }
+
+  // device: openings and FRI paths -> the proof image
+  void openings_paths_to_finish() {
+    const ProofLayout& PL = c.PL;
     mark("req_copy");
-    const uint32_t* req = d_req;
+    const uint32_t* req = c.d_req;
     // the openings and the FRI paths write disjoint sections of the proof image
     // and are both latency-bound small grids: the openings run on the side
     // stream beside the path kernel, and (single device) their section (~70% of
     // the proof) goes back over PCIe from there while the paths still run
     mark("col_open");
-    fork(st, st2, ev_fold);
-    if (stage_ev) HIP_OR_THROW(hipEventRecord(oev[0], st2));
-    ok(launch_col_open(st2, T, d_tmpl, d_outer, outer_stride, logChunks, req + 3 * max_fri_req, (int)no_grid, PL,
-                       d_tabs, d_dlev, d_dplans, d_dtabs, d_dcols),
+    fork(st, st2, c.ev_fold);
+    if (opt.stage_events) HIP_OR_THROW(hipEventRecord(c.oev[0], st2));
+    ok(launch_col_open(st2, c.T, c.d_tmpl, c.d_outer, c.outer_stride, sp.logChunks, req + 3 * c.max_fri_req, (int)no,
+                       PL, c.d_tabs, c.d_dlev, c.d_dplans, c.dict.d_dtabs, c.d_dcols),
        "col_open");
-    if (stage_ev) HIP_OR_THROW(hipEventRecord(oev[1], st2));
+    if (opt.stage_events) HIP_OR_THROW(hipEventRecord(c.oev[1], st2));
     rec(ST_OPEN + 1);
     mark("col_open_issued");
-    if (!sharded) HIP_OR_THROW(hipMemcpyAsync(h_proof + hdr_bytes, PL.base, PL.fr_off, hipMemcpyDeviceToHost, st2));
-    HIP_OR_THROW(hipEventRecord(ev_tail, st2));
+    if (!sharded)
+      HIP_OR_THROW(hipMemcpyAsync(c.h_proof + c.hdr_bytes, PL.base, PL.fr_off, hipMemcpyDeviceToHost, st2));
+    HIP_OR_THROW(hipEventRecord(c.ev_tail, st2));
     mark("open_d2h_issued");
-    ok(launch_fri_paths(st, d_layers, req, (int)nf_grid, PL), "fri_paths");
+    ok(launch_fri_paths(st, c.d_layers, req, (int)nf, PL), "fri_paths");
     mark("fri_paths_issued");
     if (sharded) {
-      HIP_OR_THROW(hipStreamWaitEvent(st, ev_tail, 0));  // the openings are part of the byte-sum
-      coll("proof_allreduce", 2 * P1 * PL.total / (uint64_t)world, [&] { comm->allreduce_sum_u8(PL.base, PL.total, st); });
+      HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_tail, 0));  // the openings are part of the byte-sum
+      coll("proof_allreduce", 2 * P1 * PL.total / (uint64_t)c.world,
+           [&] { c.comm->allreduce_sum_u8(PL.base, PL.total, st); });
     }
     rec(ST_PATHS + 1);
     const uint64_t d2h_from = sharded ? 0 : PL.fr_off;
-    HIP_OR_THROW(hipMemcpyAsync(h_proof + hdr_bytes + d2h_from, (const uint8_t*)PL.base + d2h_from,
+    HIP_OR_THROW(hipMemcpyAsync(c.h_proof + c.hdr_bytes + d2h_from, (const uint8_t*)PL.base + d2h_from,
                                 PL.total - d2h_from, hipMemcpyDeviceToHost, st));
     mark("proof_d2h_issued");
-    HIP_OR_THROW(hipMemcpyAsync(h_small + 8 * (k + 1), lvals[k], 8, hipMemcpyDeviceToHost, st));
-    if (!sharded) HIP_OR_THROW(hipStreamWaitEvent(st, ev_tail, 0));
+    HIP_OR_THROW(hipMemcpyAsync(c.h_small + 8 * (k + 1), c.lvals[k], 8, hipMemcpyDeviceToHost, st));
+    if (!sharded) HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_tail, 0));
     mark("issued");
-  };
+  }
 
-  enqueue_A();
-  sync();
-  mark("sync1");
-  host_1();
-  enqueue_B();
-  sync();
-  mark("sync2");
-  host_2();
-  enqueue_C();
-  sync();
-  mark("sync3");
-  host_3();
-  enqueue_D(nf, no);
-  sync();
-  mark("sync4");
-  if (htrace) {
-    for (auto& m : hmarks) fprintf(stderr, "%s %.1f ", m.first, m.second);
-    fprintf(stderr, "\n");
-  }
-  for (int s = 0; s <= ST_NSTAGE; s++) stage_ms[s] = 0;
-  if (stage_ev) {
-    for (int s = 0; s < ST_NSTAGE; s++) {
-      float ms = 0;
-      if (hipEventElapsedTime(&ms, ev[s], ev[s + 1]) == hipSuccess) stage_ms[s] = ms;
+  // host: stage times, the host-written fields, the dictionary bookkeeping
+  size_t finish() {
+    if (opt.host_trace) {
+      for (auto& m : hmarks) fprintf(stderr, "%s %.1f ", m.first, m.second);
+      fprintf(stderr, "\n");
     }
-    // col_openings = the openings kernel's own time on the side stream (it
-    // overlaps fri_paths); the host's query round trip before it (roots D2H,
-    // transcript, requests) falls in no stage, only in `total`
-    float oms = 0;
-    stage_ms[ST_OPEN] = hipEventElapsedTime(&oms, oev[0], oev[1]) == hipSuccess ? oms : 0.0;
-    float tot = 0;
-    (void)hipEventElapsedTime(&tot, ev[0], ev[ST_NSTAGE]);
-    stage_ms[ST_NSTAGE] = tot;
+    for (int s = 0; s <= ST_NSTAGE; s++) c.stage_ms[s] = 0;
+    if (opt.stage_events) {
+      for (int s = 0; s < ST_NSTAGE; s++) {
+        float ms = 0;
+        if (hipEventElapsedTime(&ms, c.ev[s], c.ev[s + 1]) == hipSuccess) c.stage_ms[s] = ms;
+      }
+      // col_openings = the openings kernel's own time on the side stream (it
+      // overlaps fri_paths); the host's query round trip before it (roots D2H,
+      // transcript, requests) falls in no stage, only in `total`
+      float oms = 0;
+      c.stage_ms[ST_OPEN] = hipEventElapsedTime(&oms, c.oev[0], c.oev[1]) == hipSuccess ? oms : 0.0;
+      float tot = 0;
+      (void)hipEventElapsedTime(&tot, c.ev[0], c.ev[ST_NSTAGE]);
+      c.stage_ms[ST_NSTAGE] = tot;
+    }
+    {
+      float ms = 0;
+      c.kernel_ms = kdone && hipEventElapsedTime(&ms, c.kev[0], c.kev[1]) == hipSuccess ? ms : 0.0;
+    }
+    c.have_times = true;
+    // an event pair not recorded on this path fails above; that error must not
+    // surface as the next launch's hipGetLastError()
+    (void)hipGetLastError();
+    const auto t_ser = clk::now();
+    write_host_fields(c.h_proof + c.hdr_bytes, c.PL, rows, pos.data(), roots.data(),
+                      reinterpret_cast<const uint8_t*>(c.h_small + 8 * (k + 1)), mroot);
+    const size_t out = c.hdr_bytes + c.PL.total;
+    const auto t_end = clk::now();
+    c.host_ms[0] = std::chrono::duration<double, std::milli>(t_end - t_enter).count();
+    c.host_ms[1] = t_sync;
+    c.host_ms[2] = t_last;
+    c.host_ms[3] = std::chrono::duration<double, std::milli>(t_end - t_ser).count();
+    c.have_plans = true;  // d_dplans: this proof's plans (sezkp_ctx_dict_plans)
+    c.pwstat_by_value = st_pw_by_value;
+    c.pwstat_units = st_pw_units;
+    c.dict.end_proof(du, c.dict_info, hw_obs, st_rebuilt, st_entries);
+    return out;
   }
-  {
-    float ms = 0;
-    kernel_ms = kdone && hipEventElapsedTime(&ms, kev[0], kev[1]) == hipSuccess ? ms : 0.0;
+
+  size_t run() {
+    begin();
+    columns_to_challenges();
+    sync();
+    mark("sync1");
+    read_column_challenges();
+    lde_layer0_to_betas();
+    sync();
+    mark("sync2");
+    read_betas();
+    fri_to_queries();
+    sync();
+    mark("sync3");
+    read_queries();
+    openings_paths_to_finish();
+    sync();
+    mark("sync4");
+    return finish();
   }
-  have_times = true;
-  // an event pair not recorded on this path fails above; that error must not
-  // surface as the next launch's hipGetLastError()
-  (void)hipGetLastError();
-  // ---- host-known parts of the body: counts, query headers, FRI roots,
-  // positions, final value (prover.rs:242-243), manifest root
-  const auto t_ser = clk::now();
-  uint8_t* body = h_proof + hdr_bytes;
-  auto put64 = [&](uint64_t at, uint64_t v) { memcpy(body + at, &v, 8); };
-  put64(0, NUM_QUERIES);
-  for (int q = 0; q < NUM_QUERIES; q++) {
-    put64(8 + q * PL.q_bytes, rows[q]);
-    put64(8 + q * PL.q_bytes + 8, tau);
+};
+}  // namespace
+
+size_t sezkp_ctx::prove(const uint8_t mroot[32]) {
+  if (broken)
+    throw Err{SEZKP_E_DEVICE, "context unusable: an earlier prove aborted the communicator after a failure past "
+                              "its first collective, or could not clear a tripped guard word (destroy the context "
+                              "and create a new one)"};
+  coll_issued = false;
+  coll_used = 0;
+  coll_stats.clear();
+  try {
+    if (!loaded) throw Err{SEZKP_E_INVALID, "no trace uploaded"};
+    have_plans = false;
+    ProofRun run(*this, mroot);
+    HIP_OR_THROW(hipSetDevice(device));
+    return run.run();
+  } catch (...) {
+    // peers may already be waiting in a collective this rank will never join
+    // (or this rank in one they never join): abort so that every rank's
+    // enqueued collectives stop and every rank returns an error
+    if (sharded() && coll_issued) {
+      // the stall test hook models a collective stuck on a dead peer; RCCL's
+      // abort makes such a kernel exit, so the hook's wait ends here too
+      // (ncclCommAbort would otherwise wait behind a stream nothing releases)
+      if (stall_word) __atomic_store_n(stall_word, 1u, __ATOMIC_SEQ_CST);
+      comm->abort();
+      broken = true;
+    }
+    throw;
   }
-  put64(PL.fr_off, (uint64_t)k + 1);
-  memcpy(body + PL.fr_off + 8, roots.data(), roots.size());
-  put64(PL.fq_off, NUM_QUERIES);
-  for (int q = 0; q < NUM_QUERIES; q++) {
-    const uint64_t at = PL.fq_off + 8 + q * PL.fq_bytes;
-    put64(at, (uint64_t)k + 1);
-    for (int r = 0; r <= k; r++) put64(at + 8 + 8 * r, pos[(size_t)q * (k + 1) + r]);
-    put64(at + 8 + 8 * (uint64_t)(k + 1), (uint64_t)k);
-  }
-  memcpy(body + PL.tail_off, h_small + 8 * (k + 1), 8);
-  memcpy(body + PL.tail_off + 8, mroot, 32);
-  const size_t out = hdr_bytes + PL.total;
-  const auto t_end = clk::now();
-  host_ms[0] = std::chrono::duration<double, std::milli>(t_end - t_enter).count();
-  host_ms[1] = t_sync;
-  host_ms[2] = t_last;
-  host_ms[3] = std::chrono::duration<double, std::milli>(t_end - t_ser).count();
-  have_plans = true;  // d_dplans: this proof's plans (sezkp_ctx_dict_plans)
-  dict_dirty = false;  // every table launch of this proof ran: its keys may validate
-  dstat_rebuilt = st_rebuilt;
-  dstat_reused = (uint32_t)n_dict - st_rebuilt;
-  dstat_entries = st_entries;
-  pwstat_by_value = st_pw_by_value;
-  pwstat_units = st_pw_units;
-  // the wide head ladders: what this proof saw feeds the next proof's decision
-  hw_stats.clear();
-  for (int c = 0; c < n_dict && hw_cols.size() == (size_t)n_dict; c++) {
-    if (dict_info[(size_t)c].kind != 6) continue;
-    head_wide_observe(hw_cols[c], dict_epoch, hw_obs[c]);
-    const HeadWideDev& r = hw_recs[c];
-    const bool in_place = r.epoch == dict_epoch && r.span != 0;
-    sezkp_head_wide_info s{};
-    s.col = dict_info[(size_t)c].col;
-    s.tape = dict_info[(size_t)c].tape;
-    s.origin = in_place ? r.olo : 0;
-    s.span = in_place ? r.span : 0;
-    s.dR = in_place ? r.dR : 0;
-    s.R = hw_obs[c].hi >= hw_obs[c].lo ? (uint64_t)(hw_obs[c].hi - hw_obs[c].lo) + 1 : 0;
-    s.entries_built = hw_built[c];
-    s.groups_wide = hw_obs[c].wide;
-    s.groups_fallback = (uint64_t)hw_obs[c].fb_start + hw_obs[c].fb_span;
-    s.groups_out_of_span = hw_obs[c].fb_span;
-    s.table_bytes = in_place ? hwtabs_nodes * 32 : 0;
-    hw_stats.push_back(s);
-  }
-  return out;
 }
 
 // ==================================================================== C ABI
@@ -2849,7 +2907,7 @@ int32_t sezkp_ctx_verify_batch(sezkp_ctx* ctx, const sezkp_proof_ref* proofs, ui
 int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max) {
   if (!ctx || !out_ms) return 0;
   int32_t k = 0;
-  for (; k < SEZKP_VERIFY_TIMES && k < max; k++) out_ms[k] = ctx->vfy_ms[k];
+  for (; k < SEZKP_VERIFY_TIMES && k < max; k++) out_ms[k] = ctx->vfy.vfy_ms[k];
   return k;
 }
 
@@ -2958,9 +3016,9 @@ int32_t sezkp_ctx_dict_cache_stats(const sezkp_ctx* cctx, uint32_t* cols_rebuilt
   if (!ctx || !cols_rebuilt || !cols_reused || !entries_rebuilt) return SEZKP_E_INVALID;
   if (ctx->busy()) return SEZKP_E_INVALID;  // the counts are rewritten by the proof in flight
   const bool have = ctx->loaded && ctx->have_plans && ctx->n_dict != 0;
-  *cols_rebuilt = have ? ctx->dstat_rebuilt : 0;
-  *cols_reused = have ? ctx->dstat_reused : 0;
-  *entries_rebuilt = have ? ctx->dstat_entries : 0;
+  *cols_rebuilt = have ? ctx->dict.stat_rebuilt : 0;
+  *cols_reused = have ? ctx->dict.stat_reused : 0;
+  *entries_rebuilt = have ? ctx->dict.stat_entries : 0;
   return SEZKP_OK;
 }
 int32_t sezkp_ctx_head_wide_stats(const sezkp_ctx* cctx, sezkp_head_wide_info* out, int32_t max) {
@@ -2968,8 +3026,8 @@ int32_t sezkp_ctx_head_wide_stats(const sezkp_ctx* cctx, sezkp_head_wide_info* o
   if (!ctx || (max > 0 && !out) || max < 0) return SEZKP_E_INVALID;
   if (ctx->busy()) return SEZKP_E_INVALID;  // the records are rewritten by the proof in flight
   if (!ctx->loaded || !ctx->have_plans) return 0;
-  const int32_t cnt = std::min<int32_t>(max, (int32_t)ctx->hw_stats.size());
-  for (int32_t i = 0; i < cnt; i++) out[i] = ctx->hw_stats[(size_t)i];
+  const int32_t cnt = std::min<int32_t>(max, (int32_t)ctx->dict.hw_stats.size());
+  for (int32_t i = 0; i < cnt; i++) out[i] = ctx->dict.hw_stats[(size_t)i];
   return cnt;
 }
 int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* cctx, uint32_t* cols_by_value, uint32_t* cols_by_block,
@@ -3065,7 +3123,7 @@ int32_t sezkp_stark_v1_prove(const sezkp_block_view* blocks, const uint8_t manif
   if (rc == SEZKP_OK) rc = sezkp_ctx_prove(ctx, manifest_root, flags, proof_bytes, err, err_len);
   if (rc == SEZKP_OK && meta_json) {
     try {
-      to_buf(meta_to_json(meta_for(ctx->N, ctx->tau, flags)), meta_json);
+      to_buf(meta_to_json(meta_for(ctx->sp.N, ctx->sp.tau, flags)), meta_json);
     } catch (const Err& e) {
       set_err(err, err_len, e.msg);
       rc = e.code;
@@ -3085,7 +3143,7 @@ int32_t sezkp_stark_v1_air_audit(const sezkp_block_view* blocks, sezkp_air_audit
   if (!ctx) return SEZKP_E_DEVICE;
   int32_t rc = sezkp_ctx_upload(ctx, blocks, err, err_len);
   if (rc == SEZKP_OK) {
-    const size_t bytes = (size_t)((ctx->n + 7) / 8);
+    const size_t bytes = (size_t)((ctx->sp.n + 7) / 8);
     std::vector<uint8_t> vb(violating_bits ? bytes : 0), rb(rejectable_bits ? bytes : 0);
     rc = sezkp_ctx_air_audit(ctx, out, violating_bits ? vb.data() : nullptr, rejectable_bits ? rb.data() : nullptr,
                              err, err_len);

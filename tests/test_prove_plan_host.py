@@ -4,7 +4,9 @@ sanitizers, prints the plan of a trace shape as JSON; nothing is loaded into
 Python. Checked: the planned proof length against the oracle's proofs, the FRI
 workspace's regions (inside their buffers, disjoint, tiling the totals), the
 forest's workgroup ranges and the upper-job ranges, the shape errors' texts,
-and the column work lists."""
+the column work lists, the layout of the status words that come home with the
+column roots, and the query requests (plan_requests, csrc/proof_host.h) over
+the ranks of one world."""
 import json
 import os
 import subprocess
@@ -294,3 +296,81 @@ def test_one_node_cap_job_smallest_shape(plan):
     for world in (2, 4, 8):
         assert plan(2, "logn:0", "onecap", world=world, sharded=True)["onecap"]["logn"] == -1
     assert plan(2, "logn:0", "onecap")["onecap"]["logn"] == -1
+
+
+# ------------------------------------------------------------ status words
+@pytest.mark.parametrize("use_dict", [True, False])
+@pytest.mark.parametrize("tau", [1, 2, 8])
+def test_status_layout_tiles(plan, tau, use_dict):
+    """The small copy that comes home with the column roots (StatusLayout):
+    roots, 16 guard words with the trace root at +8, 2 words per dictionary
+    column, 1 per column, HW_STAT_WORDS per dictionary column, nothing else."""
+    out = plan(tau, uniform(4096, 512), "columns,status", use_dict=use_dict)
+    c, s = out["columns"], out["status"]
+    ncols, nd = 3 + 7 * tau, len(c["dcols"])
+    assert (s["ncols"], s["n_dict"]) == (ncols, nd)
+    assert nd == ((1 + 4 * tau) if use_dict else 0)
+    assert (s["guard_words"], s["hw_stat_words"]) == (16, 10)
+    tiles([(s["roots"], 8 * ncols), (s["guard"], 16), (s["dict"], 2 * nd), (s["pw"], ncols), (s["hw"], 10 * nd)],
+          s["total"], "status words")
+    assert s["roots"] == 0 and s["trace_root"] == s["guard"] + 8
+    assert s["total"] == 8 * ncols + 16 + (2 + 10) * nd + ncols  # the size the four places spelled out by hand
+
+
+# ---------------------------------------------------------------- requests
+REQ_SHAPES = [(logn, 1, False) for logn in (0, 4, 9, 10, 12)] + \
+             [(logn, P, True) for P in (1, 2, 4, 8) for logn in (12 + P.bit_length() - 1, 13 + P.bit_length() - 1)]
+
+
+@pytest.mark.parametrize("tau", [1, 2])
+@pytest.mark.parametrize("logn,P,sharded", REQ_SHAPES, ids=lambda v: str(int(v)))
+def test_requests_partition_the_proof(plan, logn, P, sharded, tau):
+    """plan_requests over the ranks of one world: every FRI path record and
+    every column opening of the proof is requested by exactly one rank, the
+    one that owns it, within the room the proof plan allots."""
+    n, N, k, NQ = 1 << logn, 8 << logn, logn + 3, 30
+    seed = 1000 * logn + 10 * P + tau
+    fri_ords, open_ords = [], []
+    pos = None
+    for rank in range(P):
+        out = plan(tau, uniform(n, min(n, 256)), "shape,requests:%d" % seed, rank=rank, world=P, sharded=sharded)
+        s, r = out["shape"], out["requests"]
+        assert (r["max_fri_req"], r["max_open_req"]) == (NQ * 2 * k, NQ * (9 * tau + 3))
+        assert r["nf"] <= r["max_fri_req"] and r["no"] <= r["max_open_req"]
+        assert (len(r["fri"]), len(r["open"])) == (r["nf"], r["no"])
+        assert all(x < n for x in r["rows"]) and all(x < N for x in r["frows"])
+        # positions: the same on every rank, pos[q][r + 1] = pos[q][r] mod (N >> (r + 1))
+        p = [r["pos"][q * (k + 1):(q + 1) * (k + 1)] for q in range(NQ)]
+        assert pos is None or p == pos
+        pos = p
+        for q in range(NQ):
+            assert p[q][0] == r["frows"][q]
+            for l in range(k):
+                assert p[q][l + 1] == p[q][l] % (N >> (l + 1))
+        # FRI records: (layer, index, ordinal), the run owner for layers <= rR, rank 0 above them
+        for layer, idx, ordn in r["fri"]:
+            q, rem = divmod(ordn, 2 * k)
+            assert layer == rem // 2
+            assert idx == p[q][layer] ^ ((rem % 2) * (N >> (layer + 1)))
+            owner = (idx >> 12) & (P - 1) if sharded and layer <= s["rR"] else 0
+            assert owner == rank
+            fri_ords.append(ordn)
+        # openings: in proof order, by the owner of the row's chunk
+        per_q = 9 * tau + 3
+        for col, row, ordn, dict_ix in r["open"]:
+            ch = row >> 10 if n >= 1024 else 0
+            assert s["ch_lo"] <= ch < s["ch_hi"]
+            q, j = divmod(ordn, per_q)
+            row_q = r["rows"][q]
+            nxt = row_q + 1 if row_q + 1 < n else 0
+            if j < 9 * tau:
+                t, f = divmod(j, 9)
+                want_col = 3 + [0, 0, 1, 2, 3, 3, 4, 5, 6][f] * tau + t
+                want_row = nxt if f in (1, 5) else row_q
+            else:
+                want_col, want_row = [1, 2, 0][j - 9 * tau], row_q
+            assert (col, row) == (want_col, want_row)
+            assert dict_ix == r["dict_of"][col]
+            open_ords.append(ordn)
+    assert sorted(fri_ords) == list(range(NQ * 2 * k))
+    assert sorted(open_ords) == list(range(NQ * (9 * tau + 3)))

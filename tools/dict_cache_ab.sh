@@ -13,7 +13,8 @@
 # Each step has its own time limit; the first failure ends the script.
 # The same A/B serves any change that has an off switch:
 #   SEZKP_AB_OUT=<dir>       output directory (default out/dict_cache)
-#   SEZKP_AB_OFF=<VAR=value> the third headline arm's switch (default SEZKP_DICT_CACHE=0)
+#   SEZKP_AB_OFF=<VAR=value> the third headline arm's switch (default SEZKP_DICT_CACHE=0;
+#                            none: a change without a switch, such as a refactor, has no third arm)
 #   SEZKP_AB_STEPS="prof ab full"  the steps to run (default all three)
 set -euo pipefail
 export TMPDIR=/tmp
@@ -63,6 +64,7 @@ for i in $(seq 1 $R); do
   timeout -k 10 200 python3 bench.py > $O/ab/parent_$i.json 2> $O/ab/parent_$i.err
   cd $ROOT
   timeout -k 10 200 python3 bench.py > $O/ab/new_$i.json 2> $O/ab/new_$i.err
+  [ "$OFF" = none ] && continue
   env $OFF timeout -k 10 200 python3 bench.py > $O/ab/new_cache_off_$i.json 2> $O/ab/new_cache_off_$i.err
 done
 for i in $(seq 1 $RF); do

@@ -8,7 +8,9 @@ of one arm in the session.
     python3 tools/dict_cache_report.py [--off-label VAR=value] <ab dir>
 
 --off-label names the third arm's switch when the A/B ran with another one
-(tools/dict_cache_ab.sh, SEZKP_AB_OFF).
+(tools/dict_cache_ab.sh, SEZKP_AB_OFF). Without runs of a third arm
+(SEZKP_AB_OFF=none) the table has two arms and the verdict is the equality
+rule: the new arm not worse than the parent beyond the same-arm spread.
 """
 import glob
 import json
@@ -38,16 +40,28 @@ def verdict(name, new, base):
           + ("a gain by the project's bar" if every and mean_gain > spread else "NOT a gain by the project's bar"))
 
 
+def equality(new, base):
+    """A change without a switch (a refactor): the claim is equality, so the
+    new arm must not be below the parent by more than the larger difference
+    between two runs of one arm, the rule of the --full views."""
+    mean_change = (sum(new.values()) / len(new)) / (sum(base.values()) / len(base)) - 1
+    spread = max((max(a.values()) - min(a.values())) / (sum(a.values()) / len(a)) for a in (new, base))
+    print(f"new vs parent (equality claimed): mean change {100 * mean_change:+.2f}%, largest same-arm spread "
+          f"{100 * spread:.2f}% -> " + ("WORSE beyond the spread" if -mean_change > spread else "not worse beyond the spread"))
+
+
 def main(d, off_label="SEZKP_DICT_CACHE=0"):
     par, new, off = values(d, "parent"), values(d, "new"), values(d, "new_cache_off")
     print("value, 1e9 field-elements/s (plain `python bench.py`, 200 steps, 3 proofs in flight), runs alternating")
-    print(f"pair   parent      new  new, {off_label}")
+    print("pair   parent      new" + (f"  new, {off_label}" if off else ""))
     for i in sorted(new):
-        print(f"{i:4d}  {par.get(i, float('nan')):7.3f}  {new[i]:7.3f}  {off.get(i, float('nan')):7.3f}")
+        print(f"{i:4d}  {par.get(i, float('nan')):7.3f}  {new[i]:7.3f}" + (f"  {off[i]:7.3f}" if i in off else ""))
     for name, a in (("parent", par), ("new", new), ("switch off", off)):
         if a:
             print(f"{name:10s} mean {sum(a.values()) / len(a):.3f}  min {min(a.values()):.3f}  max {max(a.values()):.3f}")
-    if par:
+    if par and not off:  # tools/dict_cache_ab.sh with SEZKP_AB_OFF=none
+        equality(new, par)
+    elif par:
         verdict("new vs parent", new, par)
     if off:
         verdict(f"new vs new with {off_label}", new, off)

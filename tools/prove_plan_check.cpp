@@ -1,11 +1,16 @@
-// prove_plan_check.cpp — the upload's planning arithmetic (prove_plan.h) as a
+// prove_plan_check.cpp — the upload's planning arithmetic (prove_plan.h) and
+// a proof's request lists (plan_requests, proof_host.h) as a
 // stand-alone host program (no GPU, no ROCm headers, no Python): prints the
 // plan of one trace shape as JSON, for tests/test_prove_plan_host.py.
 //
 //   g++ -std=c++17 -g -O1 -fsanitize=address,undefined -o prove_plan_check tools/prove_plan_check.cpp
 //   ./prove_plan_check TAU RANK WORLD SHARDED USE_DICT WHAT STEP_START...
 //
-// WHAT: a comma list of shape, columns, fri, proof, onecap. STEP_START: the nblk + 1
+// WHAT: a comma list of shape, columns, fri, proof, status, requests:SEED,
+// onecap. status: the layout of the small copy that comes home with the
+// column roots (StatusLayout). requests:SEED: the path and opening requests
+// this rank owns and every query's positions (plan_requests, proof_host.h)
+// for query rows drawn from SEED. STEP_START: the nblk + 1
 // block boundaries, or the one word logn:L for the shape of 2^L rows without
 // block boundaries (shape, fri and proof only; the shard's chunks and blocks
 // are not planned). A shape the planner rejects prints {"error": "..."} and
@@ -20,6 +25,7 @@
 #include <string>
 #include <vector>
 
+#include "../streaming-zero-knowledge-proofs_amd/csrc/proof_host.h"
 #include "../streaming-zero-knowledge-proofs_amd/csrc/prove_plan.h"
 
 using namespace sezkp;
@@ -46,6 +52,8 @@ int main(int argc, char** argv) {
   const bool sharded = atoi(argv[4]) != 0, use_dict = atoi(argv[5]) != 0;
   const std::string what = std::string(",") + argv[6] + ",";
   auto want = [&](const char* w) { return what.find(std::string(",") + w + ",") != std::string::npos; };
+  long long req_seed = -1;  // requests:SEED
+  if (const size_t at = what.find(",requests:"); at != std::string::npos) req_seed = atoll(what.c_str() + at + 10);
   if (world < 1 || world > 8 || (world & (world - 1)) || rank < 0 || rank >= world) {
     fprintf(stderr, "world must be a power of two <= 8 and 0 <= rank < world\n");
     return 1;
@@ -184,6 +192,56 @@ int main(int argc, char** argv) {
         }
       printf("]}");
       sep = ", ";
+    }
+    if (only_logn < 0 && (want("status") || req_seed >= 0)) {
+      const ColumnPlan c = plan_columns(s, ss.data(), use_dict);
+      if (want("status")) {
+        const StatusLayout L = plan_status(s.ncols, (int)c.dcols.size());
+        printf("%s\"status\": {\"ncols\": %d, \"n_dict\": %zu, \"roots\": %zu, \"guard\": %zu, \"trace_root\": %zu, "
+               "\"dict\": %zu, \"pw\": %zu, \"hw\": %zu, \"total\": %zu, \"guard_words\": %d, \"hw_stat_words\": %d}",
+               sep, s.ncols, c.dcols.size(), L.roots, L.guard, L.trace_root, L.dict, L.pw, L.hw, L.total, GUARD_WORDS,
+               HW_STAT_WORDS);
+        sep = ", ";
+      }
+      if (req_seed >= 0) {
+        // rows / frows as the transcript would draw them: any values below n / N
+        uint64_t x = (uint64_t)req_seed;
+        auto next = [&]() {  // splitmix64
+          uint64_t z = (x += 0x9e3779b97f4a7c15ULL);
+          z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ULL;
+          z = (z ^ (z >> 27)) * 0x94d049bb133111ebULL;
+          return z ^ (z >> 31);
+        };
+        uint64_t rows[NUM_QUERIES], frows[NUM_QUERIES];
+        for (int q = 0; q < NUM_QUERIES; q++) rows[q] = next() % s.n;
+        for (int q = 0; q < NUM_QUERIES; q++) frows[q] = next() % s.N;
+        const ProofPlan pp = plan_proof(s, c.labels);
+        const int k = s.logN;
+        std::vector<uint64_t> pos((size_t)NUM_QUERIES * (k + 1));
+        // one word more than planned on each list: a request past the plan's room would land there, not outside
+        std::vector<uint32_t> fri(3 * (pp.max_fri_req + 1)), open((size_t)OPEN_REQ_WORDS * (pp.max_open_req + 1));
+        const RequestCounts cnt = plan_requests(s, c.dict_of.data(), rows, frows, pos.data(), fri.data(), open.data());
+        printf("%s\"requests\": {\"nf\": %zu, \"no\": %zu, \"max_fri_req\": %zu, \"max_open_req\": %zu, ", sep, cnt.nf,
+               cnt.no, pp.max_fri_req, pp.max_open_req);
+        put_list("rows", std::vector<uint64_t>(rows, rows + NUM_QUERIES));
+        printf(", ");
+        put_list("frows", std::vector<uint64_t>(frows, frows + NUM_QUERIES));
+        printf(", ");
+        put_list("pos", pos);
+        printf(", ");
+        put_list("dict_of", c.dict_of);
+        printf(", \"fri\": [");
+        for (size_t i = 0; i < cnt.nf && i <= pp.max_fri_req; i++)
+          printf("%s[%u,%u,%u]", i ? "," : "", fri[3 * i], fri[3 * i + 1], fri[3 * i + 2]);
+        printf("], \"open\": [");
+        for (size_t i = 0; i < cnt.no && i <= pp.max_open_req; i++) {
+          const uint32_t* rq = &open[(size_t)OPEN_REQ_WORDS * i];
+          printf("%s[%u,%llu,%u,%u]", i ? "," : "", rq[0], (unsigned long long)rq[1] | (unsigned long long)rq[2] << 32,
+                 rq[3], rq[4]);
+        }
+        printf("]}");
+        sep = ", ";
+      }
     }
     if (want("proof")) {
       const ProofPlan p = plan_proof(s, labels);
