@@ -2,7 +2,7 @@
 // constants, the query request lists and the proof fields the host writes.
 // Integers and BLAKE3 only: no HIP, nothing but host_crypto.h and
 // prove_plan.h, so tools/proof_host_check.cpp and tools/prove_plan_check.cpp
-// run it on a machine without a GPU. ProofRun (prover.cpp) calls these
+// run it on a machine without a GPU. ProofRun (proof_run.cpp) calls these
 // between its device phases; every rank of a sharded proof replays the same
 // transcript, so the challenges need no broadcast.
 #pragma once

@@ -1,6 +1,6 @@
 // prove_plan.h — the arithmetic of sezkp_ctx::upload as pure functions: from
 // the trace's shape (tau, block boundaries, rank, P) to sizes and ELEMENT
-// OFFSETS, no device pointer and no HIP call. upload (prover.cpp) runs the
+// OFFSETS, no device pointer and no HIP call. upload (ctx_upload.cpp) runs the
 // planners, allocates from their totals and binds pointers as base + offset;
 // tools/prove_plan_check.cpp prints the same plans on a machine without a GPU.
 // A shape the prover does not take throws PlanError (SEZKP_E_INVALID).

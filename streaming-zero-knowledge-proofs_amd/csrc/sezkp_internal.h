@@ -322,7 +322,7 @@ struct DevChal {
   uint64_t beta[FS_MAX_BETAS];      // derive_betas_for_fri (params.rs:109-119)
 };
 
-// kernels launched by the host orchestrator (prover.cpp)
+// kernels launched by the host orchestrator (proof_run.cpp, ctx_*.cpp)
 // blocks [blk_lo, blk_lo + blk_cnt) only (a sharded rank's rows + one row of halo)
 // row-major step arrays [n][tau] -> tape-major trace image [tau][n], rows [r0, r1)
 hipError_t launch_trace_image(hipStream_t st, const int8_t* raw_mv, const uint8_t* raw_hw, const uint16_t* raw_ws,
@@ -378,7 +378,7 @@ struct VerifyJobDev;
 struct VerifyLabel;
 hipError_t launch_verify_chains(hipStream_t st, const uint8_t* bytes, const VerifyJobDev* jobs, const uint8_t* roots,
                                 const VerifyLabel* labels, uint32_t njobs, uint32_t* result);
-// Sharded LDE layout change (prover.cpp, enqueue_B): cyclic coset
+// Sharded LDE layout change (proof_run.cpp, enqueue_B): cyclic coset
 // values of rank g (index g + P*j) <-> runs of S = 2^12 consecutive indices.
 hipError_t launch_cyc_pack(hipStream_t st, const uint64_t* cyc, uint64_t* send, uint64_t M, int logP);
 hipError_t launch_cyc_unpack(hipStream_t st, const uint64_t* recv, uint64_t* local, uint64_t M, int logP);

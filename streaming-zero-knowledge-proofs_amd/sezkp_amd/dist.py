@@ -7,7 +7,7 @@
   so several ranks can share one GPU in tests. Production uses RCCL inside
   the library (comm="rccl"). The replica headline's barrier and max-over-
   ranks timing live in bench.py; the sharded prover's caps are built inside
-  the library (prover.cpp, allgathered run roots).
+  the library (proof_run.cpp, allgathered run roots).
 """
 from __future__ import annotations
 
