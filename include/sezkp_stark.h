@@ -301,18 +301,58 @@ typedef struct sezkp_trace_view {
  * view or array, b = 0, tau > 255, more than 2^32 - 1 blocks and the shape
  * errors are answered before any device call. A block whose head leaves the
  * i32 range fails with the message of prove and leaves the context usable
- * (without a trace). Sharded contexts: SEZKP_E_INVALID. */
+ * (without a trace).
+ * Sharded contexts (sezkp_ctx_create_sharded*; rank-alone ones of world > 1
+ * included: a rank-alone context of ONE rank stands for no rank of a sharded
+ * proof and keeps refusing a raw trace with SEZKP_E_INVALID): the
+ * view holds the whole trace and the rank copies only the rows it reads
+ * (sezkp_trace_shard_rows). The upload performs no collective, so an error on
+ * one rank cannot block a peer: the FIRST PROOF of the image partitions the
+ * rank's own blocks on its GPU, and the ranks exchange the input-head
+ * offsets (collective "trace_in_head", an allgather of 8 bytes per rank) and
+ * the manifest leaves ("manifest_leaves", one byte-sum allreduce over 32 bytes
+ * per block); later proofs of the image run neither. Every rank computes the
+ * same manifest root. A head outside i32 then fails that proof on every rank,
+ * at the collective guard check. More than 40 tapes (the device hashes a leaf
+ * as one BLAKE3 chunk): SEZKP_E_INVALID, before any device call. */
 int32_t sezkp_ctx_upload_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len);
+/* The same from a view whose step arrays hold only rows [row0, row0 + nrows)
+ * (index 0 = row row0; t, tau and b stay global), as sezkp_ctx_upload_rows for
+ * block views: a sharded rank's slice. The slice must contain every row the
+ * context reads (sezkp_trace_shard_rows; SEZKP_E_INVALID "step arrays hold
+ * rows [...) but this context needs rows [...)" otherwise, before any device
+ * call); one device needs the whole trace. Host or device arrays. */
+int32_t sezkp_ctx_upload_trace_rows(sezkp_ctx* ctx, const sezkp_trace_view* trace, uint64_t row0, uint64_t nrows,
+                                    char* err, size_t err_len);
+/* Host only: what sezkp_shard_rows returns for the uniform block boundaries
+ * of partition_trace(t, b), without a step_start array of n_blocks + 1 words:
+ * the rows [*row0, *row0 + *nrows) that rank `rank` of `world` reads. */
+int32_t sezkp_trace_shard_rows(uint64_t t, uint32_t b, int32_t rank, int32_t world, uint64_t* row0, uint64_t* nrows);
+/* ... and its blocks: [*blk_lo, *blk_lo + *blk_cnt) are the blocks over those
+ * rows (sezkp_shard_rows' blocks); [*own_lo, *own_lo + *own_cnt) the blocks
+ * the rank OWNS: those whose first row lies in the rank's own chunks' rows.
+ * Every block has exactly one owner, the owner holds all of the block's rows,
+ * and a rank may own none (*own_cnt = 0). The owner sums the block's input
+ * moves and hashes its manifest leaf.
+ * Both: SEZKP_E_INVALID for a null pointer, b = 0, a t that is no power of
+ * two, world not in {1, 2, 4, 8}, a rank outside [0, world), or
+ * t < 4096 * world with world > 1. */
+int32_t sezkp_trace_shard_blocks(uint64_t t, uint32_t b, int32_t rank, int32_t world, uint32_t* blk_lo,
+                                 uint32_t* blk_cnt, uint32_t* own_lo, uint32_t* own_cnt);
 /* sezkp_ctx_stage for a trace of the uploaded shape (tau, block count and
  * block boundaries; the image in place may have come as blocks or as a trace,
  * and a block view may be staged on a trace context). Only the copies of the
  * four step arrays go on the copy stream; the proof that takes the image
  * partitions it, once, on its own streams. Lifetime of the arrays: as for
- * sezkp_ctx_stage. */
+ * sezkp_ctx_stage. Sharded contexts: SEZKP_E_INVALID. */
 int32_t sezkp_ctx_stage_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len);
 /* Reports on the trace image the proofs read. All three: SEZKP_E_INVALID while
  * a proof is in flight, with a staged trace no prove has consumed, or when
- * the image was uploaded as blocks.
+ * the image was uploaded as blocks. On a sharded context the root and the
+ * leaves are reported once a proof of the image has completed (before that:
+ * SEZKP_E_INVALID, "prove first"; a report starts no collective, which a call
+ * made by one rank only would block in), and sezkp_ctx_trace_blocks is
+ * SEZKP_E_INVALID: a rank holds only its own blocks' tables.
  * The manifest root: commit_blocks (lib.rs:214-222, the batch merkle_root), or
  * with frontier != 0 the Frontier root (lib.rs:167-208) that .jsonl block
  * files are committed with, computed on the host from the leaves. */
@@ -473,6 +513,8 @@ int32_t sezkp_ctx_verify_times(const sezkp_ctx* ctx, double* out_ms, int32_t max
 /* ------------------------------------------------ sharded proving (one proof, P GPUs)
  * One process per GPU; every rank uploads the same blocks and calls prove()
  * with the same manifest root; every rank returns the identical proof bytes.
+ * (Or every rank uploads the raw trace, sezkp_ctx_upload_trace /
+ * sezkp_ctx_upload_trace_rows, and proves with SEZKP_FLAG_ROOT_FROM_TRACE.)
  * P must be a power of two <= 8 with n >= 4096 * P rows. The LDE domain is
  * split into P cosets (no communication), one all-to-all moves it to a run
  * layout (rank d owns indices i with (i mod 4096P) / 4096 == d), Merkle
@@ -511,7 +553,10 @@ sezkp_ctx* sezkp_ctx_create_sharded_solo(int32_t device, int32_t rank, int32_t w
  * Per-collective device time of the last sharded prove (HIP events around
  * each call on the prover stream) and the bytes this rank sent over the links
  * (allgather (P-1) x its part, all-to-all (P-1) x the per-peer part, allreduce
- * 2 (P-1)/P x the buffer). Returns the number of entries written. */
+ * 2 (P-1)/P x the buffer). The proof that partitions a trace image
+ * (sezkp_ctx_upload_trace on a sharded context) lists two more, first:
+ * "trace_in_head" ((P-1) x 8 bytes) and "manifest_leaves" (2 (P-1)/P x 32
+ * bytes per block). Returns the number of entries written. */
 typedef struct sezkp_comm_stat {
   char name[32];
   uint64_t bytes;

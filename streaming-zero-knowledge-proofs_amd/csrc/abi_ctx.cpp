@@ -128,6 +128,15 @@ int32_t sezkp_ctx_upload_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, ch
     ctx->upload_trace(*trace);
   });
 }
+int32_t sezkp_ctx_upload_trace_rows(sezkp_ctx* ctx, const sezkp_trace_view* trace, uint64_t row0, uint64_t nrows,
+                                    char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !trace) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    if (nrows == ~0ull) throw Err{SEZKP_E_INVALID, "upload_trace_rows: nrows out of range"};
+    ctx->upload_trace(*trace, row0, nrows);
+  });
+}
 int32_t sezkp_ctx_stage_trace(sezkp_ctx* ctx, const sezkp_trace_view* trace, char* err, size_t err_len) {
   return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
     if (!ctx || !trace) throw Err{SEZKP_E_INVALID, "null argument"};

@@ -12,6 +12,7 @@
 #include "abi_util.h"
 #include "codec.h"
 #include "host_crypto.h"
+#include "trace_plan.h"
 
 using namespace sezkp;
 
@@ -37,6 +38,26 @@ int32_t sezkp_manifest_root(const sezkp_block_view* blocks, uint8_t out[32]) {
 int32_t sezkp_manifest_frontier_root(const sezkp_block_view* blocks, uint8_t out[32]) {
   if (!blocks || !out) return SEZKP_E_INVALID;
   manifest_frontier_root(*blocks, out);
+  return SEZKP_OK;
+}
+
+// a sharded rank's rows and blocks of a raw trace (trace_plan.h: what
+// sezkp_shard_rows gives for the uniform boundaries of (t, b), in closed form)
+int32_t sezkp_trace_shard_rows(uint64_t t, uint32_t b, int32_t rank, int32_t world, uint64_t* row0, uint64_t* nrows) {
+  TraceShard s;
+  if (!row0 || !nrows || !trace_shard_plan(t, b, rank, world, s)) return SEZKP_E_INVALID;
+  *row0 = s.row0;
+  *nrows = s.nrows;
+  return SEZKP_OK;
+}
+int32_t sezkp_trace_shard_blocks(uint64_t t, uint32_t b, int32_t rank, int32_t world, uint32_t* blk_lo,
+                                 uint32_t* blk_cnt, uint32_t* own_lo, uint32_t* own_cnt) {
+  TraceShard s;
+  if (!blk_lo || !blk_cnt || !own_lo || !own_cnt || !trace_shard_plan(t, b, rank, world, s)) return SEZKP_E_INVALID;
+  *blk_lo = s.blk_lo;
+  *blk_cnt = s.blk_cnt;
+  *own_lo = s.own_lo;
+  *own_cnt = s.own_cnt;
   return SEZKP_OK;
 }
 

@@ -49,12 +49,17 @@ void sezkp_ctx::alloc_trace_meta(TraceSlot& t) {
   m.tile_sum = dalloc<int64_t>((size_t)trace_scan_tiles(nblk) + 1);
   const uint64_t scratch = manifest_tree_scratch_nodes(nblk);
   m.lvl = scratch ? dalloc<uint32_t>((size_t)scratch * 8) : nullptr;
+  m.rank_tot = sharded() ? dalloc<int64_t>(8) : nullptr;
   t.root = dalloc<uint32_t>(8);
 }
 
-void sezkp_ctx::write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy) {
+// rows [r0, r0 + nr) of the image from tv, whose arrays start at row src_row0
+void sezkp_ctx::write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy,
+                                  uint64_t src_row0, uint64_t r0, uint64_t nr) {
   const uint64_t n = sp.n;
-  const size_t cells = (size_t)sp.tau * n;
+  const uint32_t tau = sp.tau;
+  const size_t cells = (size_t)tau * n;
+  if (nr == ~0ull) nr = n - r0;
   wait_copy_stream();
   HIP_OR_THROW(hipEventSynchronize(t.ready));
   auto cp = [&](void* dst, const void* src, size_t bytes) {
@@ -64,26 +69,54 @@ void sezkp_ctx::write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipS
     const bool dev = on_device(src, device);
     copy_chunked(dst, src, bytes, dev ? bytes : COPY_CHUNK, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
   };
-  cp(t.raw, tv.wsym, cells * 2);
-  cp(t.raw + 2 * cells, tv.mv, cells);
-  cp(t.raw + 3 * cells, tv.has_write, cells);
-  cp(t.imv, tv.input_mv, n);
+  const size_t c0 = (size_t)r0 * tau, nc = (size_t)nr * tau, s0 = (size_t)(r0 - src_row0) * tau;
+  cp(t.raw + 2 * c0, nc ? tv.wsym + s0 : nullptr, nc * 2);
+  cp(t.raw + 2 * cells + c0, nc ? tv.mv + s0 : nullptr, nc);
+  cp(t.raw + 3 * cells + c0, nc ? tv.has_write + s0 : nullptr, nc);
+  cp(t.imv + r0, tv.input_mv + (r0 - src_row0), nr);
   t.tm.t = tv.t;
   t.tm.b = tv.b;
   if (staged_copy) t.image_pending = true;
-  else launch_image(t, s, 0, n);
+  else launch_image(t, s, r0, nr);
 }
 
-void sezkp_ctx::upload_trace(const sezkp_trace_view& tv) {
-  if (sharded())
-    throw Err{SEZKP_E_INVALID, "upload_trace: not on a sharded context (partition the trace and upload its blocks)"};
+// Every check of a trace upload, on the host, before any device call: the
+// view, the shape (the planner's own errors), a sharded context's tape limit
+// and the slice against the rows this context reads.
+void sezkp_ctx::upload_trace(const sezkp_trace_view& tv, uint64_t row0, uint64_t nrows) {
+  // A rank-alone context stands for one rank of a P-rank proof, to measure
+  // that rank's cost; with one rank there is no peer to leave out, and such a
+  // context has always refused a raw trace. That refusal stays: the
+  // single-device context (or a one-rank communicator) takes the trace.
+  if (sharded() && world == 1 && comm->name() == "solo")
+    throw Err{SEZKP_E_INVALID, "upload_trace: not on a rank-alone sharded context of one rank (it stands for no rank of "
+                               "a sharded proof: use sezkp_ctx_create, or a rank of world > 1)"};
   check_trace_view(&tv);
+  const uint64_t nblk = trace_nblk(tv.t, tv.b);
+  if (sharded() && !manifest_leaf_on_device(tv.tau))
+    throw Err{SEZKP_E_INVALID, "upload_trace: a sharded context takes at most " +
+                                   std::to_string(MANIFEST_LEAF_DEV_MAX_TAU) +
+                                   " tapes (the device hashes a manifest leaf as one BLAKE3 chunk; got " +
+                                   std::to_string(tv.tau) + ")"};
+  TraceShard sh;
+  try {
+    (void)shape_of_logn(tv.tau, (uint32_t)nblk, ilog2(tv.t), rank, logP, sharded());
+  } catch (const PlanError& e) {
+    throw Err{SEZKP_E_INVALID, e.msg};
+  }
+  if (!trace_shard_plan(tv.t, tv.b, sharded() ? rank : 0, sharded() ? world : 1, sh))
+    throw Err{SEZKP_E_INVALID, "upload_trace: the trace's shape cannot be sharded over this context's ranks"};
+  if (nrows == ~0ull) nrows = tv.t - (row0 < tv.t ? row0 : tv.t);
+  if (row0 > sh.row0 || nrows > tv.t || row0 > tv.t - nrows || row0 + nrows < sh.row0 + sh.nrows)
+    throw Err{SEZKP_E_INVALID, "step arrays hold rows [" + std::to_string(row0) + ", " + std::to_string(row0 + nrows) +
+                                   ") but this context needs rows [" + std::to_string(sh.row0) + ", " +
+                                   std::to_string(sh.row0 + sh.nrows) + ")"};
   const std::vector<uint64_t> ss = uniform_step_start(tv.t, tv.b);
   sezkp_block_view v{};
   v.n_blocks = (uint32_t)(ss.size() - 1);
   v.tau = tv.tau;
   v.step_start = ss.data();
-  upload(v, 0, ~0ull, &tv);
+  upload(v, row0, nrows, &tv);
 }
 
 void sezkp_ctx::stage_trace(const sezkp_trace_view& tv) {
@@ -120,10 +153,10 @@ void sezkp_ctx::run_trace_tables() {
   TraceSlot& t = slot[active];
   HIP_OR_THROW(hipSetDevice(device));
   HIP_OR_THROW(launch_expand(st, T, 0, nblk, d_err));
-  HIP_OR_THROW(launch_block_tables(st, T, t.tm, t.bw, t.bi, t.bo));
+  HIP_OR_THROW(launch_block_tables(st, T, t.tm, t.bw, t.bi, t.bo, 0, nblk));
   HIP_OR_THROW(launch_inhead_scan(st, T.input_mv, t.tm, nblk));
   if (manifest_leaf_on_device(tau)) {
-    HIP_OR_THROW(launch_manifest_leaves(st, t.tm, tau, nblk));
+    HIP_OR_THROW(launch_manifest_leaves(st, t.tm, tau, 0, nblk));
   } else {
     std::vector<uint8_t> meta(trace_meta_bytes()), lv((size_t)nblk * 32);
     HIP_OR_THROW(hipMemcpyAsync(meta.data(), t.meta, meta.size(), hipMemcpyDeviceToHost, st));
@@ -181,6 +214,11 @@ sezkp_ctx::TraceSlot& sezkp_ctx::require_trace_image(const char* who) {
   TraceSlot& t = slot[active];
   if (!t.from_trace)
     throw Err{SEZKP_E_INVALID, std::string(who) + ": the active trace image was uploaded as blocks"};
+  // a sharded image is partitioned by its first proof, where every rank takes
+  // part in the two collectives; a report must not start them on its own
+  if (t.tables_pending && sharded())
+    throw Err{SEZKP_E_INVALID, std::string(who) + ": on a sharded context the first proof of a trace image partitions "
+                                                  "it and commits its manifest (prove first)"};
   if (t.tables_pending) run_trace_tables();
   return t;
 }
@@ -219,6 +257,8 @@ void sezkp_ctx::trace_manifest_root(int32_t frontier, uint8_t out[32]) {
 // arrays from `steps` (host or device memory) or back from the device
 void sezkp_ctx::trace_blocks(const sezkp_trace_view* steps, BlockStore& s) {
   const uint64_t n = sp.n;
+  if (sharded())
+    throw Err{SEZKP_E_INVALID, "trace_blocks: not on a sharded context (a rank holds only its own blocks' tables)"};
   const uint32_t tau = sp.tau, nblk = sp.nblk;
   TraceSlot& t = require_trace_image("trace_blocks");
   if (steps) {

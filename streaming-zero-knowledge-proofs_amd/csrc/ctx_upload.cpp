@@ -125,7 +125,7 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
   free_all(true);
   const UploadPlans p = plan_upload(v, row0, nrows, tv != nullptr);
   upload_trace_image(v, row0, nrows, tv);
-  upload_columns(p.cp);
+  upload_columns(p.cp, sharded() && tv != nullptr);
   upload_fri_workspace(p.fp);
   upload_proof_image(p.pp);
   if (tv) {
@@ -136,7 +136,11 @@ void sezkp_ctx::upload(const sezkp_block_view& v_in, uint64_t row0, uint64_t nro
     // upload_columns' memsets of the guard and status words (null stream),
     // before the prover stream writes behind them
     HIP_OR_THROW(hipStreamSynchronize(nullptr));
-    run_trace_tables();
+    // sharded: no collective in an upload (an error on one rank must not
+    // block a peer), so the first proof partitions the image; the caller's
+    // arrays are free once the copies are done
+    if (sharded()) HIP_OR_THROW(hipStreamSynchronize(st));
+    else run_trace_tables();
   }
   release_spares();
   loaded = true;
@@ -211,7 +215,17 @@ void sezkp_ctx::upload_trace_image(const sezkp_block_view& v, uint64_t row0, uin
   if (tv) {
     // the one synchronisation of a trace upload is run_trace_tables' (upload)
     alloc_trace_meta(slot[0]);
-    write_trace_steps(slot[0], *tv, st, false);
+    // only the rows of the blocks this context reads (all of them on one device)
+    const uint64_t need0 = v.step_start[sp.blk_lo], need1 = v.step_start[sp.blk_lo + sp.blk_cnt];
+    write_trace_steps(slot[0], *tv, st, false, row0, need0, need1 - need0);
+    TraceShard sh;
+    // the closed form against shard_range's blocks; the owned blocks inside them
+    const bool planned = trace_shard_plan(tv->t, tv->b, sharded() ? rank : 0, sharded() ? world : 1, sh);
+    if (!planned || sh.blk_lo != sp.blk_lo || sh.blk_cnt != sp.blk_cnt || sh.own_lo < sh.blk_lo ||
+        sh.own_lo + (uint64_t)sh.own_cnt > sh.blk_lo + (uint64_t)sh.blk_cnt)
+      throw Err{SEZKP_E_INVALID, "upload_trace: the rank's blocks do not match the shape's plan"};
+    own_lo = sh.own_lo;
+    own_cnt = sh.own_cnt;
   } else {
     write_trace(slot[0], v, st, row0, nrows);
     HIP_OR_THROW(hipStreamSynchronize(st));
@@ -238,7 +252,7 @@ void sezkp_ctx::bind_trace_slot(const TraceSlot& t) {
 }
 
 // ---- column templates, tables and work lists (ColumnPlan)
-void sezkp_ctx::upload_columns(const ColumnPlan& cp) {
+void sezkp_ctx::upload_columns(const ColumnPlan& cp, bool shard_root) {
   const uint64_t n = sp.n;
   const int ncols = sp.ncols;
   labels = cp.labels;
@@ -252,7 +266,7 @@ void sezkp_ctx::upload_columns(const ColumnPlan& cp) {
   for (int c = 0; c < ncols; c++)
     if (tm[c].kind >= 7) pw_blk_cols.push_back((uint32_t)c);
   // column roots, then the guard and status words behind them: one D2H copy (StatusLayout)
-  SL = plan_status(ncols, (int)dcols.size());
+  SL = plan_status(ncols, (int)dcols.size(), shard_root);
   d_colroots = dalloc<uint32_t>(SL.total);
   d_err = d_colroots + SL.guard;
   d_dstatus = d_colroots + SL.dict;

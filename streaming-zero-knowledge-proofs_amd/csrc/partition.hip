@@ -13,6 +13,16 @@
 // k_expand (trace.hip) has already written the block-local heads and their
 // per-block range (TraceDev::head, head_rng); the layouts host and device
 // share are in trace_plan.h.
+//
+// Windows and head offsets are block-local, so a sharded rank partitions the
+// blocks it reads and nothing else: every kernel takes a sub-range of blocks
+// (all of them on one device). Two things cross ranks, both exchanged by the
+// proof that partitions the image (ProofRun::shard_manifest): the input head,
+// a prefix sum of input_mv over the whole trace (each rank sums the blocks it
+// owns, the totals are allgathered, and the tile scan starts from the sum of
+// the totals of the ranks before it), and the manifest (each rank hashes the
+// leaves of the blocks it owns into a zero-filled [nblk][32] array; a byte-sum
+// allreduce completes it on every rank, and every rank reduces the tree).
 #include "dev_common.h"
 #include "sezkp_internal.h"
 #include "trace_plan.h"
@@ -26,12 +36,16 @@ static_assert(PT_THREADS == 256, "the scans below take four waves of 64 lanes");
 // One lane per (tape, block), tape-major as head_rng and the piecewise-column
 // tables are: window, window length (openings.rs:217) and head offsets into
 // the tables TraceDev reads ([tau][nblk], canonical field values) and into the
-// metadata image ([nblk][tau], the order of sezkp_block_view).
+// metadata image ([nblk][tau], the order of sezkp_block_view). Only blocks
+// [blk_lo, blk_lo + blk_cnt): all of them on one device, the blocks a sharded
+// rank reads (k_expand wrote the heads of no other).
 __global__ void __launch_bounds__(PT_THREADS) k_block_tables(TraceDev T, TraceMetaDev M, uint64_t* __restrict__ bw,
-                                                             uint64_t* __restrict__ bi, uint64_t* __restrict__ bo) {
-  const uint64_t i = (uint64_t)blockIdx.x * PT_THREADS + threadIdx.x;
-  if (i >= (uint64_t)T.tau * T.nblk) return;
-  const uint64_t r = i / T.nblk, k = i % T.nblk;
+                                                             uint64_t* __restrict__ bi, uint64_t* __restrict__ bo,
+                                                             uint32_t blk_lo, uint32_t blk_cnt) {
+  const uint64_t j = (uint64_t)blockIdx.x * PT_THREADS + threadIdx.x;
+  if (j >= (uint64_t)T.tau * blk_cnt) return;
+  const uint64_t r = j / blk_cnt, k = blk_lo + j % blk_cnt;
+  const uint64_t i = r * T.nblk + k;
   const int64_t lo = T.head_rng[2 * i], hi = T.head_rng[2 * i + 1];
   const uint64_t e = T.blk_start[k + 1];  // > blk_start[k]: a partition has no empty block
   const int64_t last = T.head[r * T.n + e - 1];
@@ -79,24 +93,28 @@ __device__ __forceinline__ int64_t wg_scan_i64(int64_t x, int64_t* sh, int64_t& 
   return x + before;
 }
 
-// blk_sum[k] = sum of input_mv over block k's rows; moves are any i8.
+// blk_sum[k] = sum of input_mv over block k's rows, for the cnt blocks from
+// k0 (all of them on one device, the blocks a sharded rank owns); moves are
+// any i8.
 // WAVE: one wave per block (lanes stride the rows, four rows per load where
 // the block starts on a 4-byte boundary), else one lane per block.
 template <bool WAVE>
 __global__ void __launch_bounds__(PT_THREADS) k_inhead_block_sums(const int8_t* __restrict__ imv, uint64_t t,
-                                                                  uint64_t b, uint64_t nblk,
+                                                                  uint64_t b, uint64_t k0, uint64_t cnt,
                                                                   int64_t* __restrict__ blk_sum) {
   if constexpr (!WAVE) {
-    const uint64_t k = (uint64_t)blockIdx.x * PT_THREADS + threadIdx.x;
-    if (k >= nblk) return;
+    const uint64_t j = (uint64_t)blockIdx.x * PT_THREADS + threadIdx.x;
+    if (j >= cnt) return;
+    const uint64_t k = k0 + j;
     const uint64_t s = trace_step_start(k, t, b), e = trace_step_start(k + 1, t, b);
     int64_t acc = 0;
     for (uint64_t r = s; r < e; r++) acc += imv[r];
     blk_sum[k] = acc;
   } else {
     const int lane = threadIdx.x & 63;
-    const uint64_t k = (uint64_t)blockIdx.x * (PT_THREADS / 64) + (threadIdx.x >> 6);
-    if (k >= nblk) return;  // whole waves leave together
+    const uint64_t j = (uint64_t)blockIdx.x * (PT_THREADS / 64) + (threadIdx.x >> 6);
+    if (j >= cnt) return;  // whole waves leave together
+    const uint64_t k = k0 + j;
     const uint64_t s = trace_step_start(k, t, b), e = trace_step_start(k + 1, t, b);
     const bool aligned = (s & 3) == 0;
     int64_t acc = 0;
@@ -113,27 +131,38 @@ __global__ void __launch_bounds__(PT_THREADS) k_inhead_block_sums(const int8_t* 
   }
 }
 
-// tile_sum[tile] = sum of the tile's block sums (trace_plan.h: the tiling)
-__global__ void __launch_bounds__(PT_THREADS) k_inhead_tile_sums(const int64_t* __restrict__ blk_sum, uint64_t nblk,
-                                                                 int64_t* __restrict__ tile_sum) {
+// tile_sum[tile] = sum of the tile's block sums (trace_plan.h: the tiling,
+// over the cnt blocks from k0). rank_total (sharded, zeroed before the
+// launch): the sum of all tiles, the word the ranks allgather.
+__global__ void __launch_bounds__(PT_THREADS) k_inhead_tile_sums(const int64_t* __restrict__ blk_sum, uint64_t k0,
+                                                                 uint64_t cnt, int64_t* __restrict__ tile_sum,
+                                                                 int64_t* __restrict__ rank_total) {
   __shared__ int64_t sh[PT_THREADS / 64];
   uint64_t lo, hi;
-  trace_scan_tile_range(blockIdx.x, nblk, lo, hi);
+  trace_scan_tile_range(blockIdx.x, cnt, lo, hi);
   int64_t acc = 0;
 #pragma unroll
   for (uint32_t j = 0; j < TRACE_SCAN_PER_LANE; j++) {
     const uint64_t k = lo + (uint64_t)threadIdx.x * TRACE_SCAN_PER_LANE + j;
-    if (k < hi) acc += blk_sum[k];
+    if (k < hi) acc += blk_sum[k0 + k];
   }
   int64_t total;
   (void)wg_scan_i64(acc, sh, total);
-  if (threadIdx.x == 0) tile_sum[blockIdx.x] = total;
+  if (threadIdx.x == 0) {
+    tile_sum[blockIdx.x] = total;
+    // two's complement: the unsigned add is the signed one
+    if (rank_total) atomicAdd(reinterpret_cast<unsigned long long*>(rank_total), (unsigned long long)total);
+  }
 }
 
-// one workgroup: tile_sum[i] becomes the sum of the tiles before tile i
-__global__ void __launch_bounds__(PT_THREADS) k_inhead_tile_scan(int64_t* __restrict__ tile_sum, uint64_t ntiles) {
+// one workgroup: tile_sum[i] becomes the sum of the tiles before tile i, from
+// the sum of rank_tot[0 .. rank) (sharded: the input head where this rank's
+// first owned block starts; at most 7 words, read by every lane)
+__global__ void __launch_bounds__(PT_THREADS) k_inhead_tile_scan(int64_t* __restrict__ tile_sum, uint64_t ntiles,
+                                                                 const int64_t* __restrict__ rank_tot, uint32_t rank) {
   __shared__ int64_t sh[PT_THREADS / 64];
   int64_t carry = 0;
+  for (uint32_t r = 0; r < rank; r++) carry += rank_tot[r];
   for (uint64_t base = 0; base < ntiles; base += PT_THREADS) {
     const uint64_t i = base + threadIdx.x;
     const int64_t v = i < ntiles ? tile_sum[i] : 0;
@@ -146,12 +175,14 @@ __global__ void __launch_bounds__(PT_THREADS) k_inhead_tile_scan(int64_t* __rest
 
 // in_head_in / in_head_out of the tile's blocks from the tile's offset
 __global__ void __launch_bounds__(PT_THREADS) k_inhead_add(const int64_t* __restrict__ blk_sum,
-                                                           const int64_t* __restrict__ tile_off, uint64_t nblk,
-                                                           int64_t* __restrict__ in_head_in,
+                                                           const int64_t* __restrict__ tile_off, uint64_t first,
+                                                           uint64_t cnt, int64_t* __restrict__ in_head_in,
                                                            int64_t* __restrict__ in_head_out) {
   __shared__ int64_t sh[PT_THREADS / 64];
   uint64_t lo, hi;
-  trace_scan_tile_range(blockIdx.x, nblk, lo, hi);
+  trace_scan_tile_range(blockIdx.x, cnt, lo, hi);
+  lo += first;  // the tiles count from the first of the cnt blocks
+  hi += first;
   const uint64_t k0 = lo + (uint64_t)threadIdx.x * TRACE_SCAN_PER_LANE;
   int64_t v[TRACE_SCAN_PER_LANE];
   int64_t mine = 0;
@@ -175,10 +206,14 @@ __global__ void __launch_bounds__(PT_THREADS) k_inhead_add(const int64_t* __rest
 // ------------------------------------------------------------ manifest leaves
 // One lane per block: the leaf message of trace_plan.h as 16-bit halves, 32 to
 // a 64-byte BLAKE3 block, chained through the chunk (b3_chunk_block). Valid
-// while the message fits one chunk (manifest_leaf_on_device).
-__global__ void __launch_bounds__(PT_THREADS) k_manifest_leaves(TraceMetaDev M, uint32_t tau, uint64_t nblk) {
-  const uint64_t k = (uint64_t)blockIdx.x * PT_THREADS + threadIdx.x;
-  if (k >= nblk) return;
+// while the message fits one chunk (manifest_leaf_on_device). The cnt blocks
+// from k0 (a sharded rank's owned blocks), each under its global index k:
+// block_id, step_lo and step_hi follow from (k, t, b).
+__global__ void __launch_bounds__(PT_THREADS) k_manifest_leaves(TraceMetaDev M, uint32_t tau, uint64_t k0,
+                                                                uint64_t cnt) {
+  const uint64_t j = (uint64_t)blockIdx.x * PT_THREADS + threadIdx.x;
+  if (j >= cnt) return;
+  const uint64_t k = k0 + j;
   LeafFields f;
   f.k = k;
   f.t = M.t;
@@ -298,35 +333,55 @@ __global__ void __launch_bounds__(PT_THREADS) k_manifest_tree(const uint32_t* __
 
 // ------------------------------------------------------------ launchers
 hipError_t launch_block_tables(hipStream_t st, const TraceDev& T, const TraceMetaDev& M, uint64_t* bw, uint64_t* bi,
-                               uint64_t* bo) {
-  const uint64_t work = (uint64_t)T.tau * T.nblk;
+                               uint64_t* bo, uint32_t blk_lo, uint32_t blk_cnt) {
+  if ((uint64_t)blk_lo + blk_cnt > T.nblk) return hipErrorInvalidValue;
+  const uint64_t work = (uint64_t)T.tau * blk_cnt;
   if (work == 0) return hipSuccess;
   hipLaunchKernelGGL(k_block_tables, dim3((unsigned)((work + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st, T,
-                     M, bw, bi, bo);
+                     M, bw, bi, bo, blk_lo, blk_cnt);
   return hipGetLastError();
+}
+
+// total: null on one device; a sharded rank's word of M.rank_tot
+hipError_t launch_inhead_sums(hipStream_t st, const int8_t* input_mv, const TraceMetaDev& M, uint64_t own_lo,
+                              uint64_t own_cnt, int64_t* total) {
+  if (own_cnt == 0) return hipSuccess;  // nothing indexes an empty range; the caller's zero is the rank's total
+  if (M.b < TRACE_SUM_WAVE_ROWS)
+    hipLaunchKernelGGL(k_inhead_block_sums<false>, dim3((unsigned)((own_cnt + PT_THREADS - 1) / PT_THREADS)),
+                       dim3(PT_THREADS), 0, st, input_mv, M.t, (uint64_t)M.b, own_lo, own_cnt, M.blk_sum);
+  else
+    hipLaunchKernelGGL(k_inhead_block_sums<true>, dim3((unsigned)((own_cnt + 3) / 4)), dim3(PT_THREADS), 0, st,
+                       input_mv, M.t, (uint64_t)M.b, own_lo, own_cnt, M.blk_sum);
+  hipLaunchKernelGGL(k_inhead_tile_sums, dim3((unsigned)trace_scan_tiles(own_cnt)), dim3(PT_THREADS), 0, st, M.blk_sum,
+                     own_lo, own_cnt, M.tile_sum, total);
+  return hipGetLastError();
+}
+
+static hipError_t inhead_offsets(hipStream_t st, const TraceMetaDev& M, uint64_t own_lo, uint64_t own_cnt,
+                                 const int64_t* rank_tot, uint32_t rank) {
+  if (own_cnt == 0) return hipSuccess;
+  const uint64_t tiles = trace_scan_tiles(own_cnt);
+  hipLaunchKernelGGL(k_inhead_tile_scan, dim3(1), dim3(PT_THREADS), 0, st, M.tile_sum, tiles, rank_tot, rank);
+  hipLaunchKernelGGL(k_inhead_add, dim3((unsigned)tiles), dim3(PT_THREADS), 0, st, M.blk_sum, M.tile_sum, own_lo,
+                     own_cnt, M.in_head_in, M.in_head_out);
+  return hipGetLastError();
+}
+hipError_t launch_inhead_offsets(hipStream_t st, const TraceMetaDev& M, uint64_t own_lo, uint64_t own_cnt,
+                                 uint32_t rank) {
+  if (rank >= 8 || !M.rank_tot) return hipErrorInvalidValue;
+  return inhead_offsets(st, M, own_lo, own_cnt, M.rank_tot, rank);
 }
 
 hipError_t launch_inhead_scan(hipStream_t st, const int8_t* input_mv, const TraceMetaDev& M, uint64_t nblk) {
-  if (nblk == 0) return hipSuccess;
-  if (M.b < TRACE_SUM_WAVE_ROWS)
-    hipLaunchKernelGGL(k_inhead_block_sums<false>, dim3((unsigned)((nblk + PT_THREADS - 1) / PT_THREADS)),
-                       dim3(PT_THREADS), 0, st, input_mv, M.t, (uint64_t)M.b, nblk, M.blk_sum);
-  else
-    hipLaunchKernelGGL(k_inhead_block_sums<true>, dim3((unsigned)((nblk + 3) / 4)), dim3(PT_THREADS), 0, st, input_mv,
-                       M.t, (uint64_t)M.b, nblk, M.blk_sum);
-  const uint64_t tiles = trace_scan_tiles(nblk);
-  hipLaunchKernelGGL(k_inhead_tile_sums, dim3((unsigned)tiles), dim3(PT_THREADS), 0, st, M.blk_sum, nblk, M.tile_sum);
-  hipLaunchKernelGGL(k_inhead_tile_scan, dim3(1), dim3(PT_THREADS), 0, st, M.tile_sum, tiles);
-  hipLaunchKernelGGL(k_inhead_add, dim3((unsigned)tiles), dim3(PT_THREADS), 0, st, M.blk_sum, M.tile_sum, nblk,
-                     M.in_head_in, M.in_head_out);
-  return hipGetLastError();
+  const hipError_t e = launch_inhead_sums(st, input_mv, M, 0, nblk, nullptr);
+  return e != hipSuccess ? e : inhead_offsets(st, M, 0, nblk, nullptr, 0);
 }
 
-hipError_t launch_manifest_leaves(hipStream_t st, const TraceMetaDev& M, uint32_t tau, uint64_t nblk) {
-  if (nblk == 0) return hipSuccess;
+hipError_t launch_manifest_leaves(hipStream_t st, const TraceMetaDev& M, uint32_t tau, uint64_t k0, uint64_t cnt) {
+  if (cnt == 0) return hipSuccess;
   if (!manifest_leaf_on_device(tau)) return hipErrorInvalidValue;  // the host hashes these (trace_plan.h)
-  hipLaunchKernelGGL(k_manifest_leaves, dim3((unsigned)((nblk + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st,
-                     M, tau, nblk);
+  hipLaunchKernelGGL(k_manifest_leaves, dim3((unsigned)((cnt + PT_THREADS - 1) / PT_THREADS)), dim3(PT_THREADS), 0, st,
+                     M, tau, k0, cnt);
   return hipGetLastError();
 }
 

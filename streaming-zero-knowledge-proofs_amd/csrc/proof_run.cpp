@@ -200,7 +200,9 @@ struct ProofRun {
   // column roots. A staged trace is partitioned once, by the proof that takes
   // it: k_block_tables after k_expand, the manifest kernels on the side
   // stream. More than 40 tapes: the host hashes the leaves, a round trip of
-  // its own (trace_plan.h).
+  // its own (trace_plan.h). Sharded: the first proof of an uploaded trace
+  // partitions the rank's blocks and commits the manifest with its peers
+  // (shard_manifest); the root has status words of its own there.
   sezkp_ctx::TraceSlot& img;
   const uint8_t* mroot;
   const bool root_dev;
@@ -368,6 +370,31 @@ struct ProofRun {
     }
   }
 
+  // The manifest of a sharded trace image, in the proof that partitions it, on
+  // the prover stream. Each rank sums input_mv and hashes the leaves of the
+  // blocks it owns (trace_plan.h); two things cross ranks:
+  //  * trace_in_head: 8 bytes per rank, the rank's input_mv total; the input
+  //    head at a rank's first owned block is the sum of the totals before it,
+  //    taken on the device by the tile scan;
+  //  * manifest_leaves: a byte-sum over the zero-filled [nblk][32] leaf array
+  //    (each leaf has one writer), as the proof body's: owned-block counts
+  //    differ between ranks, so an allgather would need padded parts.
+  // Every rank issues both, whatever it owns and whatever its guard word
+  // says: the guard words are read after them, at the collective check.
+  void shard_manifest() {
+    const TraceMetaDev& M = img.tm;
+    const uint64_t leaf_bytes = (uint64_t)sp.nblk * 32;
+    HIP_OR_THROW(hipMemsetAsync(M.rank_tot, 0, 8 * sizeof(int64_t), st));
+    ok(launch_inhead_sums(st, c.T.input_mv, M, c.own_lo, c.own_cnt, M.rank_tot + c.rank), "inhead_sums");
+    coll("trace_in_head", P1 * 8, [&] { c.comm->allgather(M.rank_tot + c.rank, M.rank_tot, 8, st); });
+    ok(launch_inhead_offsets(st, M, c.own_lo, c.own_cnt, (uint32_t)c.rank), "inhead_offsets");
+    HIP_OR_THROW(hipMemsetAsync(M.leaves, 0, (size_t)leaf_bytes, st));
+    ok(launch_manifest_leaves(st, M, sp.tau, c.own_lo, c.own_cnt), "manifest_leaves");
+    coll("manifest_leaves", 2 * P1 * leaf_bytes / (uint64_t)c.world,
+         [&] { c.comm->allreduce_sum_u8(M.leaves, (size_t)leaf_bytes, st); });
+    ok(launch_manifest_tree(st, M, sp.nblk, img.root, c.trace_root_words()), "manifest_tree");
+  }
+
   // device: expand, column commitments, outer trees -> column roots + status words
   void columns_to_challenges() {
     TraceDev& T = c.T;
@@ -376,7 +403,8 @@ struct ProofRun {
     // ---- column commitments (openings.rs:306-398): this rank's chunks, then
     // every rank gathers all chunk roots and builds the outer trees
     ok(launch_expand(st, T, sp.blk_lo, sp.blk_cnt, d_err), "expand");
-    if (trace_tables) ok(launch_block_tables(st, T, img.tm, img.bw, img.bi, img.bo), "block_tables");
+    if (trace_tables)
+      ok(launch_block_tables(st, T, img.tm, img.bw, img.bi, img.bo, sp.blk_lo, sp.blk_cnt), "block_tables");
     rec(1);
     // piecewise / table / dense columns on the side stream, concurrent with the
     // (VALU-bound) dictionary columns; disjoint outer-tree leaves. (Starting
@@ -396,14 +424,17 @@ struct ProofRun {
     // the manifest of a trace image behind the columns: nothing reads the
     // root before the copy of the column roots, so the dictionary commit and
     // the outer trees do not wait for it (ev_root)
-    if (trace_tables) {
+    // (a sharded image's manifest needs two collectives: shard_manifest, below)
+    const bool shard_trace = trace_tables && sharded;
+    if (trace_tables && !sharded) {
       ok(launch_inhead_scan(st2, T.input_mv, img.tm, sp.nblk), "inhead_scan");
-      ok(launch_manifest_leaves(st2, img.tm, sp.tau, sp.nblk), "manifest_leaves");
+      ok(launch_manifest_leaves(st2, img.tm, sp.tau, 0, sp.nblk), "manifest_leaves");
       ok(launch_manifest_tree(st2, img.tm, sp.nblk, img.root, d_err + 8), "manifest_tree");
       HIP_OR_THROW(hipEventRecord(c.ev_root, st2));
-    } else if (root_dev && !c.root_in_err) {
+    } else if (!trace_tables && root_dev && !c.root_in_err) {
       // the root was computed by an earlier call and a guard clear took it
-      HIP_OR_THROW(hipMemcpyAsync(d_err + 8, img.root, 32, hipMemcpyDeviceToDevice, st2));
+      // (sharded: no proof has put it into its status words yet)
+      HIP_OR_THROW(hipMemcpyAsync(c.trace_root_words(), img.root, 32, hipMemcpyDeviceToDevice, st2));
       HIP_OR_THROW(hipEventRecord(c.ev_root, st2));
     }
     // (One launch of a workgroup per column instead of the five flat launches,
@@ -420,6 +451,7 @@ struct ProofRun {
                           c.outer_stride, row_lo, row_hi - row_lo, c.d_dlev, du.dcache, opt.dict_tab_cap,
                           dict_plan_rows),
        "col_commit_dict");
+    if (shard_trace) shard_manifest();
     HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_cols, 0));
     // test hook (ProveOptions::trip_guard)
     if (opt.trip_guard && opt.trip_guard_rank == c.rank) HIP_OR_THROW(hipMemsetAsync(d_err, 0x7f, 1, st));
@@ -445,7 +477,8 @@ struct ProofRun {
     rec(3);
     // one copy: the column roots and, right behind them, the guard words
     // (sharded, every rank's word at d_err + 8) and the status words (StatusLayout)
-    if (trace_tables || (root_dev && !c.root_in_err)) HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_root, 0));
+    if (!shard_trace && (trace_tables || (root_dev && !c.root_in_err)))
+      HIP_OR_THROW(hipStreamWaitEvent(st, c.ev_root, 0));
     HIP_OR_THROW(hipMemcpyAsync(c.h_small, c.d_colroots, c.SL.total * 4, hipMemcpyDeviceToHost, st));
   }
 
@@ -458,7 +491,7 @@ struct ProofRun {
     if (trace_tables) img.tables_pending = false;
     if (trace_tables || root_dev) {
       c.root_in_err = true;
-      memcpy(c.h_root, h_small + SL.trace_root, 32);
+      memcpy(c.h_root, h_small + (sharded ? SL.shard_root : SL.trace_root), 32);
       c.h_root_valid = true;
     }
     if (root_dev) {

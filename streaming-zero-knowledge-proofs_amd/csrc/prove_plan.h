@@ -466,7 +466,8 @@ inline ProofPlan plan_proof(const ShapePlan& s, const std::vector<std::string>& 
 // [8 + r] rank r's when sharded; on a single device the eight words at +8
 // hold a trace image's manifest root), then the dictionary cache's status
 // words (k_dict_plan), one word per column for the piecewise tables' form
-// (k_col_tables) and the wide head ladder's status words. The allocation, the
+// (k_col_tables), the wide head ladder's status words and, for a sharded
+// trace image, its manifest root. The allocation, the
 // device pointers, the host buffer, the copy and its parse all read this.
 constexpr int GUARD_WORDS = 16;
 struct StatusLayout {
@@ -476,9 +477,12 @@ struct StatusLayout {
   size_t dict = 0;        // 2 words per dictionary column: rebuilt, entries
   size_t pw = 0;          // 1 word per column
   size_t hw = 0;          // HW_STAT_WORDS per dictionary column
+  // a sharded trace image only: the manifest root, eight words appended (the
+  // eight at trace_root are the ranks' guard words there); else = total
+  size_t shard_root = 0;
   size_t total = 0;
 };
-inline StatusLayout plan_status(int ncols, int n_dict) {
+inline StatusLayout plan_status(int ncols, int n_dict, bool shard_root = false) {
   StatusLayout s;
   s.roots = 0;
   s.guard = s.roots + 8 * (size_t)ncols;
@@ -486,7 +490,8 @@ inline StatusLayout plan_status(int ncols, int n_dict) {
   s.dict = s.guard + GUARD_WORDS;
   s.pw = s.dict + 2 * (size_t)n_dict;
   s.hw = s.pw + (size_t)ncols;
-  s.total = s.hw + (size_t)HW_STAT_WORDS * (size_t)n_dict;
+  s.shard_root = s.hw + (size_t)HW_STAT_WORDS * (size_t)n_dict;
+  s.total = s.shard_root + (shard_root ? 8 : 0);
   return s;
 }
 

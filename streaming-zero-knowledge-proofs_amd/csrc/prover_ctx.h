@@ -26,6 +26,7 @@
 #include "verify_plan.h"
 
 using namespace sezkp;
+static_assert(TRACE_SHARD_CHUNK_LOG2 == COL_CHUNK_LOG2, "trace_shard_plan restates shard_range's chunks");
 
 // ST_L0TREE brackets exactly one launch (k_layer16 over the LDE) so bench.py
 // can quote that kernel's live duration; ST_L0UP holds its upper levels.
@@ -297,9 +298,16 @@ struct sezkp_ctx {
   // uses) and comes home with the column roots. root_in_err: it is there (a
   // guard clear zeroes it, a switch of image replaces it); h_root: the host's
   // copy of the active image's root, when it has come home.
+  // On a sharded context those eight words are the ranks' guard words: the
+  // root rides in words of its own at the end of the status block
+  // (StatusLayout::shard_root), and root_in_err says it is there.
   bool root_in_err = false;
   uint8_t h_root[32]{};
   bool h_root_valid = false;
+  // a trace image's blocks this context owns (trace_plan.h: all of them on
+  // one device): their input_mv sums and manifest leaves are computed here
+  uint32_t own_lo = 0, own_cnt = 0;
+  uint32_t* trace_root_words() const { return sharded() ? d_colroots + SL.shard_root : d_err + 8; }
   NttTables tw{};
   // workspace of the current upload, and the previous upload's blocks kept
   // for reuse (keyed by byte size): re-uploading a trace of the same shape
@@ -503,18 +511,25 @@ struct sezkp_ctx {
   SEZKP_LOCAL UploadPlans plan_upload(const sezkp_block_view& v, uint64_t row0, uint64_t& nrows, bool from_trace);
   SEZKP_LOCAL void upload_trace_image(const sezkp_block_view& v, uint64_t row0, uint64_t nrows,
                                       const sezkp_trace_view* tv);
-  SEZKP_LOCAL void upload_columns(const ColumnPlan& cp);
+  // shard_root: a sharded trace image, whose manifest root has status words of its own
+  SEZKP_LOCAL void upload_columns(const ColumnPlan& cp, bool shard_root);
   SEZKP_LOCAL void upload_fri_workspace(const FriPlan& fp);
   SEZKP_LOCAL void upload_proof_image(const ProofPlan& pp);
   SEZKP_LOCAL void bind_trace_slot(const TraceSlot& t);  // the slot's arrays into T
-  void upload_trace(const sezkp_trace_view& tv);
+  // tv's step arrays hold rows [row0, row0 + nrows) (the whole trace by
+  // default; t, tau, b global). On a sharded context only the rank's rows are
+  // copied and the first proof partitions the image (no collective here).
+  void upload_trace(const sezkp_trace_view& tv, uint64_t row0 = 0, uint64_t nrows = ~0ull);
   void stage_trace(const sezkp_trace_view& tv);
   void alloc_trace_meta(TraceSlot& t);
   size_t trace_meta_bytes() const { return (size_t)sp.tau * sp.nblk * 24 + (size_t)sp.nblk * 16; }
-  // the four step arrays of tv (host or device memory) into slot t, async on s
-  void write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy);
+  // rows [r0, r0 + nr) of the four step arrays of tv (host or device memory,
+  // index 0 = row src_row0) into slot t, async on s
+  void write_trace_steps(TraceSlot& t, const sezkp_trace_view& tv, hipStream_t s, bool staged_copy,
+                         uint64_t src_row0 = 0, uint64_t r0 = 0, uint64_t nr = ~0ull);
   // the active trace image's block tables, metadata, leaves and root, on the
   // prover stream, synchronised; throws prove's message when a head leaves i32
+  // (one device only: a sharded image is partitioned by its first proof)
   void run_trace_tables();
   TraceSlot& require_trace_image(const char* who);
   void trace_manifest_root(int32_t frontier, uint8_t out[32]);

@@ -170,17 +170,28 @@ struct TraceMetaDev {
   int64_t* blk_sum;      // [nblk] input_mv summed per block
   int64_t* tile_sum;     // [trace_scan_tiles(nblk)]
   uint32_t* lvl;         // manifest_tree_scratch_nodes(nblk) nodes (null when 0)
+  int64_t* rank_tot;     // [8] sharded: every rank's sum of input_mv over the blocks it owns (allgathered)
 };
 // the largest manifest tree one workgroup reduces (k_manifest_tree)
 constexpr uint64_t MANIFEST_TREE_WG_LEAVES = 1ull << 14;
-// window lengths and head offsets of every (tape, block) from the heads of
-// launch_expand on the same stream, into bw / bi / bo ([tau][nblk]) and M
+// window lengths and head offsets of every (tape, block) of blocks [blk_lo,
+// blk_lo + blk_cnt) (the blocks launch_expand ran over on the same stream),
+// into bw / bi / bo ([tau][nblk]) and M; no other block's entry is touched
 hipError_t launch_block_tables(hipStream_t st, const TraceDev& T, const TraceMetaDev& M, uint64_t* bw, uint64_t* bi,
-                               uint64_t* bo);
+                               uint64_t* bo, uint32_t blk_lo, uint32_t blk_cnt);
 // M.in_head_in / in_head_out: per-block sums, tile sums, their scan, the add
 hipError_t launch_inhead_scan(hipStream_t st, const int8_t* input_mv, const TraceMetaDev& M, uint64_t nblk);
-// M.leaves from the metadata image (tau <= MANIFEST_LEAF_DEV_MAX_TAU)
-hipError_t launch_manifest_leaves(hipStream_t st, const TraceMetaDev& M, uint32_t tau, uint64_t nblk);
+// The same in two halves over the blocks a sharded rank owns (trace_plan.h),
+// [own_lo, own_lo + own_cnt): the sums, with the rank's total added to *total
+// (zeroed by the caller; own_cnt = 0 launches nothing); then, once
+// M.rank_tot holds every rank's total, the scan from the sum of the totals of
+// the ranks before `rank`, and the add.
+hipError_t launch_inhead_sums(hipStream_t st, const int8_t* input_mv, const TraceMetaDev& M, uint64_t own_lo,
+                              uint64_t own_cnt, int64_t* total);
+hipError_t launch_inhead_offsets(hipStream_t st, const TraceMetaDev& M, uint64_t own_lo, uint64_t own_cnt,
+                                 uint32_t rank);
+// M.leaves of blocks [k0, k0 + cnt) from the metadata image (tau <= MANIFEST_LEAF_DEV_MAX_TAU)
+hipError_t launch_manifest_leaves(hipStream_t st, const TraceMetaDev& M, uint32_t tau, uint64_t k0, uint64_t cnt);
 // merkle_root of M.leaves into root_a and (when not null) root_b, 8 words each
 uint64_t manifest_tree_scratch_nodes(uint64_t nblk);
 hipError_t launch_manifest_tree(hipStream_t st, const TraceMetaDev& M, uint64_t nblk, uint32_t* root_a,

@@ -28,6 +28,44 @@ TRACE_PLAN_HD inline uint64_t trace_step_start(uint64_t k, uint64_t t, uint64_t 
   return k > lim ? t : (k * b < t ? k * b : t);
 }
 
+// ------------------------------------------------------------ sharded traces
+// Rank g of P = 2^logP commits the column chunks shard_range (prove_plan.h)
+// gives it and reads the whole blocks over their rows [r0, r1] (r1: the halo
+// row). With uniform boundaries the block of a row is row / b, so a rank's
+// rows and blocks follow from (t, b) alone, without a step_start array.
+// Rank g OWNS block k exactly when the block's first row k b lies in the
+// rank's own rows [r0, r_end): every block has one owner, the owner holds all
+// of the block's rows (k b >= r0, and the block ends at or before the end of
+// the block of r1), and a rank whose rows start no block owns none. The owner
+// sums the block's input_mv and hashes its manifest leaf (partition.hip).
+constexpr int TRACE_SHARD_CHUNK_LOG2 = 10;  // = COL_CHUNK_LOG2 (prover_ctx.h asserts it)
+struct TraceShard {
+  uint64_t row0 = 0, nrows = 0;       // the rows the rank reads (whole blocks): sezkp_shard_rows
+  uint32_t blk_lo = 0, blk_cnt = 0;   // the blocks it reads
+  uint32_t own_lo = 0, own_cnt = 0;   // the blocks it owns (inside the read range)
+};
+// false: a shape the sharded prover does not take (the caller's SEZKP_E_INVALID)
+inline bool trace_shard_plan(uint64_t t, uint64_t b, int64_t rank, int64_t world, TraceShard& s) {
+  if (b == 0 || b > 0xFFFFFFFFull || t == 0 || (t & (t - 1)) != 0) return false;
+  if (world != 1 && world != 2 && world != 4 && world != 8) return false;
+  if (rank < 0 || rank >= world) return false;
+  if (world > 1 && t < 4096ull * (uint64_t)world) return false;
+  if (trace_nblk(t, b) > 0xFFFFFFFFull) return false;
+  const uint64_t chunk_rows = t < (1ull << TRACE_SHARD_CHUNK_LOG2) ? t : 1ull << TRACE_SHARD_CHUNK_LOG2;
+  const uint64_t per_rank = (t / chunk_rows) / (uint64_t)world;  // chunks per rank
+  const uint64_t r0 = per_rank * (uint64_t)rank * chunk_rows, r_end = r0 + per_rank * chunk_rows;
+  const uint64_t r1 = r_end < t - 1 ? r_end : t - 1;
+  const uint64_t lo = r0 / b, hi = r1 / b;
+  s.blk_lo = (uint32_t)lo;
+  s.blk_cnt = (uint32_t)(hi - lo + 1);
+  s.row0 = trace_step_start(lo, t, b);
+  s.nrows = trace_step_start(hi + 1, t, b) - s.row0;
+  const uint64_t o0 = (r0 + b - 1) / b, o1 = (r_end + b - 1) / b;  // first blocks starting at or after r0 / r_end
+  s.own_lo = (uint32_t)o0;
+  s.own_cnt = (uint32_t)(o1 - o0);
+  return true;
+}
+
 // ------------------------------------------------------------ input-head scan
 // in_head_in / in_head_out are the exclusive / inclusive prefix sums of the
 // blocks' input_mv sums, exact in i64. Three launches: every tile of

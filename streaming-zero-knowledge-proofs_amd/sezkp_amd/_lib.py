@@ -43,6 +43,7 @@ EXPORTS = [
     "sezkp_ctx_upload_trace", "sezkp_ctx_stage_trace", "sezkp_ctx_manifest_root", "sezkp_ctx_manifest_leaves",
     "sezkp_ctx_trace_blocks", "sezkp_stark_v1_prove_trace", "sezkp_trace_decode_cbor", "sezkp_trace_encode_cbor",
     "sezkp_trace_view_of", "sezkp_trace_free",
+    "sezkp_ctx_upload_trace_rows", "sezkp_trace_shard_rows", "sezkp_trace_shard_blocks",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -231,6 +232,10 @@ def _load():
     L.sezkp_stark_v1_verify_batch.argtypes = [C.POINTER(ProofRef), C.c_uint32, C.POINTER(VerifyResultC)] + E
     L.sezkp_ctx_verify_times.argtypes = [C.c_void_p, C.POINTER(C.c_double), C.c_int32]
     L.sezkp_ctx_upload_trace.argtypes = [C.c_void_p, C.POINTER(TraceView)] + E
+    L.sezkp_ctx_upload_trace_rows.argtypes = [C.c_void_p, C.POINTER(TraceView), C.c_uint64, C.c_uint64] + E
+    L.sezkp_trace_shard_rows.argtypes = [C.c_uint64, C.c_uint32, C.c_int32, C.c_int32, C.POINTER(C.c_uint64),
+                                         C.POINTER(C.c_uint64)]
+    L.sezkp_trace_shard_blocks.argtypes = [C.c_uint64, C.c_uint32, C.c_int32, C.c_int32] + [C.POINTER(C.c_uint32)] * 4
     L.sezkp_ctx_stage_trace.argtypes = [C.c_void_p, C.POINTER(TraceView)] + E
     L.sezkp_ctx_manifest_root.argtypes = [C.c_void_p, C.c_int32, C.c_char_p] + E
     L.sezkp_ctx_manifest_leaves.argtypes = [C.c_void_p, C.c_void_p, C.c_uint64] + E

@@ -275,6 +275,21 @@ class ProverContext:
         self.n_blocks = -(-int(v.t) // int(v.b))
         del keep  # the call is synchronous
 
+    def upload_trace_rows(self, input_mv, mv, has_write, wsym, b: int, t: int, row0: int) -> None:
+        """upload_trace from arrays that hold only rows [row0, row0 + len) of a
+        trace of t steps (sezkp_ctx_upload_trace_rows): a sharded rank's slice,
+        which must contain the rows of `trace_shard_rows(t, b, rank, world)`;
+        a single-device context needs the whole trace."""
+        if row0 < 0 or t < 0:
+            raise SezkpError(-1, "row0 and t must be non-negative")
+        v, keep = trace_view(input_mv, mv, has_write, wsym, b, getattr(self, "device", None), t=t)
+        nrows = len(keep[0])
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_upload_trace_rows(self._h, C.byref(v), row0, nrows, err, 1024), err)
+        self.tau, self.n_rows = int(v.tau), int(v.t)
+        self.n_blocks = -(-int(v.t) // int(v.b))
+        del keep  # the call is synchronous
+
     def stage_trace(self, input_mv, mv, has_write, wsym, b: int) -> None:
         """stage() for a raw movement log of the uploaded shape
         (sezkp_ctx_stage_trace); the arrays must stay unchanged until the
@@ -530,6 +545,14 @@ class ShardedProverContext(ProverContext):
     `group` by `sezkp_amd.dist.HostCollectives` — for tests on one GPU.
     comm="solo": this rank alone on `device` with its own contributions only
     (no group): the per-rank cost model; timings real, proof bytes not.
+
+    From a raw movement log: every rank calls upload_trace (the whole trace;
+    the rank copies only its rows) or upload_trace_rows (its slice,
+    `trace_shard_rows`), then prove() without a root. The first proof of the
+    image partitions each rank's blocks on its GPU and exchanges the input-head
+    offsets and the manifest leaves (collectives trace_in_head and
+    manifest_leaves in comm_stats()); manifest_root() and manifest_leaves()
+    report once a proof has completed, blocks() is not available.
     """
 
     def __init__(self, rank: int, world: int, device: int = 0, comm: str = "rccl", group=None):
@@ -537,6 +560,8 @@ class ShardedProverContext(ProverContext):
         err = C.create_string_buffer(1024)
         self.tau = 0
         self.n_rows = 0
+        self.n_blocks = 0
+        self.device = device
         self.rank, self.world = rank, world
         self._hc = None
         if comm == "rccl":

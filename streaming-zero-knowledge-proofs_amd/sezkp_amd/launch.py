@@ -21,6 +21,18 @@ manifest leaf hashes are allgathered (rank 0 reduces the leaves to the root
 and broadcasts the precheck verdict), and each rank fully decodes and uploads
 only the lines of the blocks over its own rows plus the halo row
 (--full-ingest: every rank decodes the whole file, as before).
+
+From the movement log itself (`sezkp-cli prove --trace` over several GPUs):
+
+    python -m sezkp_amd.launch prove --trace trace.cbor --b B --out proof.cbor \\
+        [--out-manifest M] [--manifest M] [--gpus P] [--comm rccl|host]
+
+Every rank decodes the TraceFile and uploads only the rows it reads
+(`upload_trace_rows`); the ranks partition their own blocks on their GPUs
+and commit the manifest together in the proof. Rank 0 writes the artifact
+and, with --out-manifest, the manifest `sezkp-cli commit` gives for the
+partitioned blocks. --manifest is compared with the root the GPUs computed
+before anything is written.
 """
 from __future__ import annotations
 
@@ -68,6 +80,60 @@ def _precheck(blocks, path: str, root: bytes, n_leaves: int) -> None:
 
 def _is_jsonl(path: str) -> bool:
     return path.rsplit(".", 1)[-1].lower() in ("jsonl", "ndjson") if "." in path else False
+
+
+def _manifest_cbor(root: bytes, n_leaves: int) -> bytes:
+    """The manifest file `sezkp-cli commit` writes: {version: 1, root, n_leaves}."""
+    from .backend import _head
+
+    def text(s: str) -> bytes:
+        return _head(3, len(s)) + s.encode()
+    return (_head(5, 3) + text("version") + _head(0, 1) + text("root") + _head(4, 32) +
+            b"".join(_head(0, x) for x in root) + text("n_leaves") + _head(0, n_leaves))
+
+
+def _trace_outputs(args, ctx, art) -> None:
+    """After the proof: --manifest must carry the root the device computed
+    (the wording of `sezkp-cli prove --trace`); then the artifact and, when
+    asked, the manifest are written."""
+    root = art.manifest_root
+    if args.manifest:
+        want, _ = _read_manifest(args.manifest)
+        if want != root:
+            raise RuntimeError(f"stark-v1 proof failed: manifest root mismatch: manifest={want.hex()}, "
+                               f"trace={root.hex()}")
+    if args.out_manifest:
+        with open(args.out_manifest, "wb") as f:
+            f.write(_manifest_cbor(root, ctx.n_blocks))
+    with open(args.out, "wb") as f:
+        f.write(art.to_cbor())
+
+
+def _trace_worker(rank: int, world: int, port: int, args, q) -> None:
+    """`prove --trace` on one rank: decode the TraceFile, upload only this
+    rank's rows (upload_trace_rows), prove without a root; rank 0 writes."""
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
+    import torch.distributed as dist
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from . import ShardedProverContext, Trace, trace_shard_rows
+        t0 = time.perf_counter()
+        tr = Trace.from_cbor(open(args.trace, "rb").read())
+        row0, nrows = trace_shard_rows(tr.t, args.b, rank, world)
+        t_load = time.perf_counter() - t0
+        ctx = ShardedProverContext(rank, world, device=0 if args.comm == "host" else rank, comm=args.comm)
+        ctx.upload_trace_rows(*(a[row0:row0 + nrows] for a in tr.arrays()), args.b, tr.t, row0)
+        t1 = time.perf_counter()
+        art = ctx.prove(streaming=args.stream)
+        t_prove = time.perf_counter() - t1
+        if rank == 0:
+            _trace_outputs(args, ctx, art)
+        ctx.close()
+        q.put((rank, None, len(art.proof_bytes), t_load, t_prove))
+    except Exception as e:  # reported by the parent
+        q.put((rank, f"{type(e).__name__}: {e}", 0, 0.0, 0.0))
+    finally:
+        dist.destroy_process_group()
 
 
 def _worker(rank: int, world: int, port: int, args, q) -> None:
@@ -159,6 +225,29 @@ def prove(args) -> int:
     if not args.out.lower().endswith(".cbor"):
         print("error: --out must be a .cbor artifact", file=sys.stderr)
         return 2
+    if args.trace:
+        if args.blocks or args.b is None or not 1 <= args.b < 1 << 32:
+            print("error: prove --trace takes --b (1..2^32-1) and no --blocks", file=sys.stderr)
+            return 2
+        if args.out_manifest and not args.out_manifest.lower().endswith(".cbor"):
+            print("error: --out-manifest must be a .cbor manifest", file=sys.stderr)
+            return 2
+    elif not args.blocks or not args.manifest or args.out_manifest:
+        print("error: prove takes --blocks and --manifest, or --trace and --b", file=sys.stderr)
+        return 2
+    if args.trace and args.gpus == 1 and args.comm == "rccl":
+        from . import ProverContext, Trace
+        try:
+            tr = Trace.from_cbor(open(args.trace, "rb").read())
+            ctx = ProverContext(0)
+            ctx.upload_trace(*tr.arrays(), args.b)
+            art = ctx.prove(streaming=args.stream)
+            _trace_outputs(args, ctx, art)
+        except Exception as e:
+            print(f"error: {e}", file=sys.stderr)
+            return 1
+        print(json.dumps({"gpus": 1, "proof_bytes": len(art.proof_bytes)}))
+        return 0
     if args.gpus == 1 and args.comm == "rccl":
         from . import ProverContext
         from .blocks import BlockSoA
@@ -180,7 +269,8 @@ def prove(args) -> int:
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
     port = _port()
-    ps = [ctx.Process(target=_worker, args=(r, args.gpus, port, args, q), daemon=True) for r in range(args.gpus)]
+    target = _trace_worker if args.trace else _worker
+    ps = [ctx.Process(target=target, args=(r, args.gpus, port, args, q), daemon=True) for r in range(args.gpus)]
     for p in ps:
         p.start()
     res, err = _collect(ps, q, args.timeout)
@@ -197,8 +287,11 @@ def main(argv=None) -> int:
     sub = ap.add_subparsers(dest="cmd", required=True)
     p = sub.add_parser("prove")
     p.add_argument("--backend", default="stark", choices=["stark"])
-    p.add_argument("--blocks", required=True)
-    p.add_argument("--manifest", required=True)
+    p.add_argument("--blocks")
+    p.add_argument("--manifest")
+    p.add_argument("--trace", help="a TraceFile (.cbor) instead of --blocks: partitioned on the GPUs into blocks of --b")
+    p.add_argument("--b", type=int, help="steps per block (with --trace)")
+    p.add_argument("--out-manifest", help="with --trace: write the manifest the GPUs committed (.cbor)")
     p.add_argument("--out", required=True)
     p.add_argument("--stream", action="store_true")
     p.add_argument("--assume-committed", action="store_true")

@@ -24,12 +24,38 @@ def _is_torch(a) -> bool:
     return type(a).__module__.split(".")[0] == "torch"
 
 
-def trace_view(input_mv, mv, has_write, wsym, b: int, device: int | None = None):
+def trace_shard_rows(t: int, b: int, rank: int, world: int) -> tuple:
+    """(row0, nrows): the rows rank `rank` of a `world`-GPU sharded prove reads
+    of a trace of t steps cut into blocks of b (sezkp_trace_shard_rows)."""
+    row0, nrows = C.c_uint64(), C.c_uint64()
+    if not (0 <= t < 1 << 64 and 0 <= b < 1 << 32):
+        raise SezkpError(-1, "trace_shard_rows: t or b out of range")
+    rc = lib.sezkp_trace_shard_rows(t, b, rank, world, C.byref(row0), C.byref(nrows))
+    if rc != 0:
+        raise SezkpError(rc, f"trace_shard_rows: invalid shape (t={t}, b={b}, rank={rank}, world={world})")
+    return row0.value, nrows.value
+
+
+def trace_shard_blocks(t: int, b: int, rank: int, world: int) -> dict:
+    """{blk_lo, blk_cnt, own_lo, own_cnt}: the blocks the rank reads and the
+    blocks it owns (sezkp_trace_shard_blocks)."""
+    w = [C.c_uint32() for _ in range(4)]
+    if not (0 <= t < 1 << 64 and 0 <= b < 1 << 32):
+        raise SezkpError(-1, "trace_shard_blocks: t or b out of range")
+    rc = lib.sezkp_trace_shard_blocks(t, b, rank, world, *[C.byref(x) for x in w])
+    if rc != 0:
+        raise SezkpError(rc, f"trace_shard_blocks: invalid shape (t={t}, b={b}, rank={rank}, world={world})")
+    return dict(zip(("blk_lo", "blk_cnt", "own_lo", "own_cnt"), (x.value for x in w)))
+
+
+def trace_view(input_mv, mv, has_write, wsym, b: int, device: int | None = None, t: int | None = None):
     """(TraceView, keep): the sezkp_trace_view of the four arrays with block
     size b, and the objects that must stay alive while the view is used.
     Torch tensors must be contiguous, of the right width and (when `device` is
     given) on that device; the current torch stream of their device is
-    synchronised, so the library's own stream reads finished data."""
+    synchronised, so the library's own stream reads finished data.
+    t: the steps of the whole trace when the arrays hold only a slice of its
+    rows (sezkp_ctx_upload_trace_rows)."""
     arrs = [input_mv, mv, has_write, wsym]
     keep, ptrs, shapes = [], [], []
     for name, a, npt in zip(_NAMES, arrs, _NP_TYPES):
@@ -52,17 +78,19 @@ def trace_view(input_mv, mv, has_write, wsym, b: int, device: int | None = None)
             keep.append(a)
             ptrs.append(a.ctypes.data if a.size else 0)
             shapes.append(a.shape)
-    t = int(shapes[0][0]) if len(shapes[0]) == 1 else -1
-    if t < 0 or len(shapes[1]) != 2 or shapes[1][0] != t:
+    rows = int(shapes[0][0]) if len(shapes[0]) == 1 else -1
+    if rows < 0 or len(shapes[1]) != 2 or shapes[1][0] != rows:
         raise SezkpError(-1, "trace: input_mv must be [t] and mv [t, tau]")
     tau = int(shapes[1][1])
     for name, sh in zip(_NAMES[2:], shapes[2:]):
-        if tuple(sh) != (t, tau):
-            raise SezkpError(-1, f"trace.{name} has shape {tuple(sh)}, expected {(t, tau)}")
+        if tuple(sh) != (rows, tau):
+            raise SezkpError(-1, f"trace.{name} has shape {tuple(sh)}, expected {(rows, tau)}")
     if not 0 <= int(b) < 1 << 32:
         raise SezkpError(-1, "trace: b must fit 32 bits")
+    if t is not None and not rows <= int(t) < 1 << 64:
+        raise SezkpError(-1, "trace: t must be at least the rows the arrays hold")
     v = TraceView()
-    v.t, v.tau, v.b = t, tau, int(b)
+    v.t, v.tau, v.b = rows if t is None else int(t), tau, int(b)
     v.input_mv, v.mv, v.has_write, v.wsym = [p or None for p in ptrs]
     return v, keep
 
