@@ -383,6 +383,81 @@ int32_t sezkp_trace_encode_cbor(const sezkp_trace_view* trace, sezkp_buf* out);
 const sezkp_trace_view* sezkp_trace_view_of(const sezkp_trace* t);
 void sezkp_trace_free(sezkp_trace* t);
 
+/* ------------------------------------------------ trace files decoded on the device
+ * sezkp_trace_decode_cbor is a single-threaded pull parser, O(t) on the host
+ * in front of the first kernel. These take the file's bytes (host memory,
+ * pinned or pageable) and decode them on the context's GPU into the four step
+ * arrays in device memory; the host never holds the decoded trace.
+ * The device path takes exactly the canonical form ciborium and
+ * sezkp_trace_encode_cbor write (csrc/trace_cbor_plan.h):
+ *   A4 | 67 "version" | uint | 63 "tau" | uint <= 255 | 65 "steps" | array(t),
+ *   t x (A2 | 68 "input_mv" | int | 65 "tapes" | array(tau) |
+ *        tau x (A2 | 65 "write" | F6 or uint | 62 "mv" | int)),
+ *   64 "meta" | one flat item (null, a number, a string), ending at len,
+ * every integer in its minimal-length head. It declines anything else, and a
+ * declined call runs sezkp_trace_decode_cbor's decoder on the host. For every
+ * input the result is what sezkp_trace_decode_cbor followed by
+ * sezkp_ctx_upload_trace gives: the same code, the same message (every
+ * decode message is the host decoder's), the same arrays (wsym = 0 where
+ * there is no write).
+ * SEZKP_TRACE_CBOR_HOST=1 (read per call) forces the host decoder.
+ * Out of scope: blocks.cbor and JSONL block files on the device (their step
+ * records are the same), a staged, pipelined form, input bytes that are
+ * already in device memory, JSON traces. */
+/* Decode, then upload as sezkp_ctx_upload_trace does with block size b. A null
+ * ctx, data or b = 0: SEZKP_E_INVALID before any device call. len = 0 with a
+ * non-null data is an empty file, not a bad argument: the decoder refuses it
+ * as sezkp_trace_decode_cbor does (SEZKP_E_DECODE, "truncated CBOR"), here and
+ * in the two entry points below. A decode failure:
+ * SEZKP_E_DECODE with the host decoder's message, the context's trace state
+ * untouched. Upload failures: as for sezkp_ctx_upload_trace. On a sharded
+ * context the rank decodes the whole file on its GPU and copies only the rows
+ * it reads; a rank-alone context of one rank refuses, as it does a raw trace. */
+int32_t sezkp_ctx_upload_trace_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, uint32_t b, char* err,
+                                    size_t err_len);
+/* The same decode, with the arrays read back into a host handle (b = 0 in its
+ * view; free with sezkp_trace_free). Needs no uploaded trace and leaves the
+ * context's trace state untouched: the parity entry point of the decoder. */
+int32_t sezkp_ctx_decode_trace_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, sezkp_trace** out, char* err,
+                                    size_t err_len);
+/* Stateless, device 0: decode + sezkp_stark_v1_prove_trace. Null data or
+ * proof_bytes and b = 0 are answered before any device is touched, and so is
+ * a file without a canonical head that the host decoder refuses. */
+int32_t sezkp_stark_v1_prove_trace_cbor(const uint8_t* data, size_t len, uint32_t b, uint32_t flags,
+                                        sezkp_buf* proof_bytes, uint8_t manifest_root_out[32], char* err,
+                                        size_t err_len);
+/* Host only: 1 and *t, *tau, *steps_off (the offset of the first step record)
+ * when the bytes start with a canonical head whose t steps can fit in the
+ * rest of the file, else 0 (also for a null argument). */
+int32_t sezkp_trace_cbor_head(const uint8_t* data, size_t len, uint64_t* t, uint32_t* tau, uint64_t* steps_off);
+/* What the last upload_trace_cbor / decode_trace_cbor call of the context did. */
+#define SEZKP_INGEST_DEVICE 0u
+#define SEZKP_INGEST_HOST 1u
+#define SEZKP_INGEST_R_NONE 0u        /* the device path decoded the file */
+#define SEZKP_INGEST_R_HEAD 1u        /* no canonical head */
+#define SEZKP_INGEST_R_CANDIDATES 2u  /* fewer than t step signatures */
+#define SEZKP_INGEST_R_STEP 3u        /* step `index` is not a canonical record */
+#define SEZKP_INGEST_R_CHAIN 4u       /* step `index` does not start where step index - 1 ends */
+#define SEZKP_INGEST_R_TAIL 5u        /* no "meta" and one flat item between the last step and len */
+#define SEZKP_INGEST_R_FORCED 6u      /* SEZKP_TRACE_CBOR_HOST=1 */
+typedef struct sezkp_trace_ingest_info {
+  uint32_t path;       /* SEZKP_INGEST_DEVICE / SEZKP_INGEST_HOST */
+  uint32_t reason;     /* SEZKP_INGEST_R_*: why the device path declined */
+  uint64_t index;      /* the step of SEZKP_INGEST_R_STEP / _CHAIN, else 0 */
+  uint64_t bytes;      /* len */
+  uint64_t t;          /* steps and tapes of the decoded trace, on either path; of a file that
+                        * was refused, those of its head (0 without a canonical head) */
+  uint32_t tau;
+  uint32_t pad;
+  uint64_t candidates; /* step signatures found (0 when the device did not look) */
+  double ms_h2d;       /* HIP events: the bytes' copy, the four kernels; 0 when not run */
+  double ms_decode;
+  double ms_host;      /* the host decoder's wall time; 0 when it did not run */
+} sezkp_trace_ingest_info;
+/* SEZKP_OK, or SEZKP_E_INVALID for a null argument, while a proof is in
+ * flight, or before the context's first decode call. */
+int32_t sezkp_ctx_trace_ingest_stats(const sezkp_ctx* ctx, sezkp_trace_ingest_info* out);
+
 /* ------------------------------------------------ full-trace AIR audit
  * Does the committed trace satisfy the AIR, on every row? The reference
  * verifier recomputes the composition (air.rs:49-136) only on its 30 opened

@@ -555,4 +555,99 @@ int32_t sezkp_stark_v1_prove_trace(const sezkp_trace_view* trace, uint32_t flags
   return rc;
 }
 
+// ---- trace files decoded on the device (ctx_trace_cbor.cpp)
+int32_t sezkp_ctx_upload_trace_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, uint32_t b, char* err,
+                                    size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !data) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (b == 0) throw Err{SEZKP_E_INVALID, "trace view: b (steps per block) must be at least 1"};
+    require_idle(ctx);
+    BlockStore host;
+    sezkp_trace_view tv{};
+    ctx->decode_trace_cbor(data, len, host, tv);
+    tv.b = b;
+    ctx->upload_trace(tv);
+  });
+}
+
+int32_t sezkp_ctx_decode_trace_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, sezkp_trace** out, char* err,
+                                    size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !data || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    std::unique_ptr<sezkp_trace> tr(new sezkp_trace());
+    sezkp_trace_view tv{};
+    ctx->decode_trace_cbor(data, len, tr->s, tv);
+    if (ctx->cbor.info.path == SEZKP_INGEST_DEVICE) {
+      const size_t t = (size_t)tv.t, cells = t * tv.tau;
+      BlockStore& s = tr->s;
+      s = BlockStore();
+      s.tau = tv.tau;
+      s.input_mv.resize(t);
+      s.mv.resize(cells);
+      s.has_write.resize(cells);
+      s.wsym.resize(cells);
+      auto get = [&](void* dst, const void* src, size_t bytes) {
+        if (bytes) HIP_OR_THROW(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->st));
+      };
+      get(s.input_mv.data(), tv.input_mv, t);
+      get(s.mv.data(), tv.mv, cells);
+      get(s.has_write.data(), tv.has_write, cells);
+      get(s.wsym.data(), tv.wsym, cells * 2);
+      HIP_OR_THROW(hipStreamSynchronize(ctx->st));
+    }
+    tr->bind();
+    *out = tr.release();
+  });
+}
+
+int32_t sezkp_ctx_trace_ingest_stats(const sezkp_ctx* cctx, sezkp_trace_ingest_info* out) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || !out || ctx->busy() || !ctx->cbor.have_info) return SEZKP_E_INVALID;
+  *out = ctx->cbor.info;
+  return SEZKP_OK;
+}
+
+// The argument checks come before any device is touched. A file without the
+// canonical head would be decoded on the host anyway: it is decoded here,
+// once, before a device is opened (so its refusal needs none), and its arrays
+// are uploaded as sezkp_stark_v1_prove_trace uploads them.
+int32_t sezkp_stark_v1_prove_trace_cbor(const uint8_t* data, size_t len, uint32_t b, uint32_t flags,
+                                        sezkp_buf* proof_bytes, uint8_t manifest_root_out[32], char* err,
+                                        size_t err_len) {
+  BlockStore host;
+  sezkp_trace_view tv{};
+  bool decoded = false;
+  const int32_t pre = guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!data || !proof_bytes) throw Err{SEZKP_E_INVALID, "null argument"};
+    if (b == 0) throw Err{SEZKP_E_INVALID, "trace view: b (steps per block) must be at least 1"};
+    TraceCborHead h;
+    if (trace_cbor_head(CborSpan{data, len}, h)) return;
+    std::string e;
+    if (!decode_trace_cbor(data, len, host, e)) throw Err{SEZKP_E_DECODE, e};
+    tv.t = host.input_mv.size();
+    tv.tau = host.tau;
+    tv.b = b;
+    tv.input_mv = host.input_mv.data();
+    tv.mv = host.mv.data();
+    tv.has_write = host.has_write.data();
+    tv.wsym = host.wsym.data();
+    check_trace_view(&tv);
+    decoded = true;
+  });
+  if (pre != SEZKP_OK) return pre;
+  sezkp_ctx* ctx = sezkp_ctx_create(0, err, err_len);
+  if (!ctx) return SEZKP_E_DEVICE;
+  int32_t rc = decoded ? sezkp_ctx_upload_trace(ctx, &tv, err, err_len)
+                       : sezkp_ctx_upload_trace_cbor(ctx, data, len, b, err, err_len);
+  if (rc == SEZKP_OK)
+    rc = sezkp_ctx_prove(ctx, nullptr, flags | SEZKP_FLAG_ROOT_FROM_TRACE, proof_bytes, err, err_len);
+  if (rc == SEZKP_OK && manifest_root_out) {
+    rc = sezkp_ctx_manifest_root(ctx, 0, manifest_root_out, err, err_len);
+    if (rc != SEZKP_OK) sezkp_buf_free(proof_bytes);
+  }
+  sezkp_ctx_destroy(ctx);
+  return rc;
+}
+
 }  // extern "C"

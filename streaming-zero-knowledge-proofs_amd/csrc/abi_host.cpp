@@ -12,6 +12,7 @@
 #include "abi_util.h"
 #include "codec.h"
 #include "host_crypto.h"
+#include "trace_cbor_plan.h"
 #include "trace_plan.h"
 
 using namespace sezkp;
@@ -62,10 +63,6 @@ int32_t sezkp_trace_shard_blocks(uint64_t t, uint32_t b, int32_t rank, int32_t w
 }
 
 // TraceFile CBOR (sezkp-trace io.rs; format.rs:59-68)
-struct sezkp_trace {
-  BlockStore s;  // the four step arrays
-  sezkp_trace_view view{};
-};
 int32_t sezkp_trace_decode_cbor(const uint8_t* data, size_t len, sezkp_trace** out, char* err, size_t err_len) {
   if (!out || (!data && len)) return SEZKP_E_INVALID;
   try {
@@ -75,13 +72,7 @@ int32_t sezkp_trace_decode_cbor(const uint8_t* data, size_t len, sezkp_trace** o
       set_err(err, err_len, e);
       return SEZKP_E_DECODE;
     }
-    t->view.t = t->s.input_mv.size();
-    t->view.tau = t->s.tau;
-    t->view.b = 0;
-    t->view.input_mv = t->s.input_mv.data();
-    t->view.mv = t->s.mv.data();
-    t->view.has_write = t->s.has_write.data();
-    t->view.wsym = t->s.wsym.data();
+    t->bind();
     *out = t.release();
     return SEZKP_OK;
   } catch (const std::exception& e) {
@@ -101,6 +92,15 @@ int32_t sezkp_trace_encode_cbor(const sezkp_trace_view* trace, sezkp_buf* out) {
   } catch (const std::exception&) {
     return SEZKP_E_NOMEM;
   }
+}
+// the canonical head the device decoder takes (trace_cbor_plan.h)
+int32_t sezkp_trace_cbor_head(const uint8_t* data, size_t len, uint64_t* t, uint32_t* tau, uint64_t* steps_off) {
+  TraceCborHead h;
+  if (!data || !t || !tau || !steps_off || !trace_cbor_head(CborSpan{data, len}, h)) return 0;
+  *t = h.t;
+  *tau = h.tau;
+  *steps_off = h.steps_off;
+  return 1;
 }
 const sezkp_trace_view* sezkp_trace_view_of(const sezkp_trace* t) { return t ? &t->view : nullptr; }
 void sezkp_trace_free(sezkp_trace* t) { delete t; }

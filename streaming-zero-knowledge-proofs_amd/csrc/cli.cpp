@@ -1,8 +1,9 @@
 // cli.cpp — `sezkp-cli` drop-in for the STARK path on MI355X:
 //   prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]
 //   prove  --backend stark --trace T.cbor --b STEPS_PER_BLOCK --out P [--out-blocks F] [--out-manifest F]
-//          [--manifest M] [--stream]
-//          (from the movement log: partition and manifest on the device; --manifest is compared with its root)
+//          [--manifest M] [--stream] [--host-decode]
+//          (from the movement log: decode, partition and manifest on the device; --manifest is compared with
+//          its root; --host-decode: the trace file is decoded on the host first, as before the device decoder)
 //   verify --backend stark --blocks B --manifest M --proof P [--assume-committed] [--gpu]
 //          (--gpu: the Merkle paths are hashed on device 0, sezkp_stark_v1_verify_batch; same output)
 //   commit --blocks B(.cbor|.json|.jsonl|.ndjson) --out M
@@ -105,7 +106,7 @@ std::string pretty_artifact(const Artifact& a) {
 
 struct Args {
   std::string cmd, backend = "stark", blocks, manifest, out, proof, input, trace, out_blocks, out_manifest;
-  bool stream = false, assume = false, json = false, gpu = false, b_given = false;
+  bool stream = false, assume = false, json = false, gpu = false, b_given = false, host_decode = false;
   std::string t = "32", b = "4", tau = "2";  // simulate defaults (main.rs:87-100)
 };
 
@@ -194,12 +195,24 @@ int cmd_prove_trace(const Args& a) {
   std::vector<uint8_t> raw;
   if (!read_file(a.trace, raw, err)) { fprintf(stderr, "Error: reading trace: %s\n", err.c_str()); return 1; }
   char msg[512] = {0};
+  // A file with the canonical head goes to the device as bytes and is decoded
+  // there (sezkp_ctx_upload_trace_cbor); any other, and every file with
+  // --host-decode, is decoded here first, as it always was.
+  uint64_t head_t = 0, head_off = 0;
+  uint32_t head_tau = 0;
+  const bool by_bytes = !a.host_decode && sezkp_trace_cbor_head(raw.data(), raw.size(), &head_t, &head_tau, &head_off) == 1;
   sezkp_trace* th = nullptr;
-  if (sezkp_trace_decode_cbor(raw.data(), raw.size(), &th, msg, sizeof msg)) {
-    fprintf(stderr, "Error: reading trace: %s\n", msg);
-    return 1;
+  sezkp_trace_view tv{};
+  if (!by_bytes) {
+    if (sezkp_trace_decode_cbor(raw.data(), raw.size(), &th, msg, sizeof msg)) {
+      fprintf(stderr, "Error: reading trace: %s\n", msg);
+      return 1;
+    }
+    tv = *sezkp_trace_view_of(th);
+  } else {
+    tv.t = head_t;
+    tv.tau = head_tau;
   }
-  sezkp_trace_view tv = *sezkp_trace_view_of(th);
   tv.b = (uint32_t)b;
   uint8_t want[32], root[32];
   const bool have_manifest = !a.manifest.empty();
@@ -213,7 +226,24 @@ int cmd_prove_trace(const Args& a) {
     }
     ctx = sezkp_ctx_create(0, msg, sizeof msg);
     if (!ctx) { fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg); break; }
-    if (sezkp_ctx_upload_trace(ctx, &tv, msg, sizeof msg) || sezkp_ctx_manifest_root(ctx, 0, root, msg, sizeof msg)) {
+    if (by_bytes) {
+      // from the pageable bytes as they were read: the context stages them
+      // through its own page-locked block (11.6 ms at the headline shape,
+      // against 8.6 ms from bytes that are page-locked already; locking 239 MB
+      // for one copy was not shown to cost less than the 3 ms it could save)
+      const int32_t urc = sezkp_ctx_upload_trace_cbor(ctx, raw.data(), raw.size(), tv.b, msg, sizeof msg);
+      if (urc == SEZKP_E_DECODE) { fprintf(stderr, "Error: reading trace: %s\n", msg); break; }
+      if (urc) { fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg); break; }
+      // the shape of what was decoded, on whichever path
+      sezkp_trace_ingest_info ii{};
+      if (sezkp_ctx_trace_ingest_stats(ctx, &ii)) { fprintf(stderr, "Error: stark-v1 proof failed: no ingest report\n"); break; }
+      tv.t = ii.t;
+      tv.tau = ii.tau;
+    } else if (sezkp_ctx_upload_trace(ctx, &tv, msg, sizeof msg)) {
+      fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg);
+      break;
+    }
+    if (sezkp_ctx_manifest_root(ctx, 0, root, msg, sizeof msg)) {
       fprintf(stderr, "Error: stark-v1 proof failed: %s\n", msg);
       break;
     }
@@ -230,7 +260,11 @@ int cmd_prove_trace(const Args& a) {
     const uint32_t nblk = (uint32_t)((tv.t + b - 1) / b);
     if (!a.out_blocks.empty()) {
       sezkp_blocks* bh = nullptr;
-      if (sezkp_ctx_trace_blocks(ctx, &tv, &bh, msg, sizeof msg)) { fprintf(stderr, "Error: %s\n", msg); break; }
+      // decoded on the device: the steps come back from there (NULL steps)
+      if (sezkp_ctx_trace_blocks(ctx, by_bytes ? nullptr : &tv, &bh, msg, sizeof msg)) {
+        fprintf(stderr, "Error: %s\n", msg);
+        break;
+      }
       sezkp_buf buf{};
       const int32_t erc = ext_lower(a.out_blocks) == "cbor" ? sezkp_blocks_encode_cbor(sezkp_blocks_view(bh), &buf)
                                                             : sezkp_blocks_encode_jsonl(sezkp_blocks_view(bh), &buf);
@@ -524,7 +558,7 @@ void usage() {
   fprintf(stderr,
           "usage: sezkp-cli prove  --backend stark --blocks B --manifest M --out P [--stream] [--assume-committed]\n"
           "       sezkp-cli prove  --backend stark --trace T.cbor --b STEPS_PER_BLOCK --out P [--out-blocks F]\n"
-          "                        [--out-manifest F] [--manifest M] [--stream]\n"
+          "                        [--out-manifest F] [--manifest M] [--stream] [--host-decode]\n"
           "       sezkp-cli verify --backend stark --blocks B --manifest M --proof P [--assume-committed] [--gpu]\n"
           "       sezkp-cli commit --blocks B --out M\n"
           "       sezkp-cli verify-commit --blocks B --manifest M\n"
@@ -555,6 +589,7 @@ int main(int argc, char** argv) {
       if (a.cmd != "prove") a.out = a.out_blocks;
     } else if (s == "--output") val(a.out);
     else if (s == "--trace") val(a.trace);
+    else if (s == "--host-decode") a.host_decode = true;
     else if (s == "--out-manifest") val(a.out_manifest);
     else if (s == "--input") val(a.input);
     else if (s == "--t") val(a.t);

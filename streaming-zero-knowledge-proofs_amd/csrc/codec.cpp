@@ -990,6 +990,27 @@ bool decode_trace_cbor(const uint8_t* data, size_t len, BlockStore& out, std::st
   }
 }
 
+// The end of a canonical TraceFile (trace_cbor_plan.h) as decode_trace_cbor
+// reads it after the last step of a definite `steps` array: the key "meta",
+// one item that skip() takes, and nothing behind it. The canonical form
+// stops at flat items (null, a number, a string): a nested meta (array, map,
+// tag) is the host decoder's, so this check never recurses.
+bool trace_cbor_tail_ok(const uint8_t* data, size_t len, size_t off) {
+  if (off > len) return false;
+  try {
+    Cbor d(data + off, len - off);
+    if (off == len || data[off] != 0x64 || d.key() != "meta") return false;
+    const size_t item = off + 5;  // 64 "meta"
+    if (item >= len) return false;
+    const int major = data[item] >> 5;
+    if (major == 4 || major == 5 || major == 6) return false;
+    d.skip();
+    return d.done();
+  } catch (const std::exception&) {
+    return false;
+  }
+}
+
 // version 1 and no meta, as generate_trace leaves them (generator.rs:38-73)
 std::vector<uint8_t> encode_trace_cbor(const sezkp_trace_view& v) {
   std::vector<uint8_t> o;

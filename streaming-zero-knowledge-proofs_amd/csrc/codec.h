@@ -42,6 +42,8 @@ void partition_trace(BlockStore& s, uint64_t t, uint32_t tau, uint32_t b, const 
 // store's step arrays and its tau (no block field is touched), and back
 bool decode_trace_cbor(const uint8_t* data, size_t len, BlockStore& out, std::string& err);
 std::vector<uint8_t> encode_trace_cbor(const sezkp_trace_view& v);
+// the bytes from `off` are the tail of a canonical TraceFile: "meta", one flat item (no array, map or tag), the end
+bool trace_cbor_tail_ok(const uint8_t* data, size_t len, size_t off);
 bool decode_manifest_cbor(const uint8_t* data, size_t len, uint8_t root[32], uint32_t* n_leaves, std::string& err);
 bool decode_manifest_json(const char* data, size_t len, uint8_t root[32], uint32_t* n_leaves, std::string& err);
 

@@ -1,7 +1,8 @@
 // prover_ctx.h — the prover context (struct sezkp_ctx) and what its units
 // share: ctx.cpp (life of a context), ctx_upload.cpp, ctx_trace.cpp,
-// ctx_services.cpp (audit, batch verify), proof_run.cpp (one proof) and the
-// C ABI in abi_ctx.cpp / abi_kernels.cpp. Internal to the library: nothing
+// ctx_trace_cbor.cpp (trace files decoded on the device), ctx_services.cpp
+// (audit, batch verify), proof_run.cpp (one proof) and the C ABI in
+// abi_ctx.cpp / abi_kernels.cpp. Internal to the library: nothing
 // outside csrc/ includes it.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -22,6 +23,7 @@
 #include "comm.h"
 #include "prove_plan.h"
 #include "sezkp_internal.h"
+#include "trace_cbor_plan.h"
 #include "trace_plan.h"
 #include "verify_plan.h"
 
@@ -68,7 +70,8 @@ struct AsyncSlot {
 //   per proof:         everything else below
 //   elsewhere:         SEZKP_NO_DICT per upload (upload), SEZKP_FORCE_SHARDED per
 //                      context (ctx_create), SEZKP_VERIFY_CHUNK_BYTES per verify
-//                      call (verify_batch)
+//                      call (verify_batch), SEZKP_TRACE_CBOR_HOST per trace-file
+//                      decode (decode_trace_cbor_device)
 struct ProveOptions {
   bool host_trace = false;   // SEZKP_HOST_TRACE=1: host-side marks printed per proof
   bool sync_debug = false;   // SEZKP_SYNC_DEBUG: sync after every launch, to name the failing kernel
@@ -209,6 +212,34 @@ struct VerifyBuffers {
   uint64_t n_vlabels = 0;
   hipEvent_t vev[4]{};
   double vfy_ms[SEZKP_VERIFY_TIMES]{};
+  void release();
+};
+
+// TraceFile CBOR decoded on the device (sezkp_ctx_upload_trace_cbor,
+// ctx_trace_cbor.cpp): the file's bytes, the tile counts and their scan, the
+// candidate offsets, the decoded step arrays (wsym | mv | has_write |
+// input_mv, one block) and the verdict words; a pinned block that pageable
+// bytes are staged through, in two halves, and a pinned landing place for the
+// verdict. Like the verifier's buffers they live outside the upload
+// workspace, grow on demand and are kept.
+struct TraceCborBuffers {
+  uint8_t* d_bytes = nullptr;
+  size_t bytes_cap = 0;
+  uint32_t* d_counts = nullptr;
+  uint64_t* d_offs = nullptr;
+  size_t tiles_cap = 0;  // tiles; the other capacities in bytes
+  uint64_t* d_cand = nullptr;
+  size_t cand_cap = 0;
+  uint8_t* d_arrays = nullptr;
+  size_t arrays_cap = 0;
+  TraceCborVerdict* d_verdict = nullptr;
+  TraceCborVerdict* h_verdict = nullptr;  // pinned
+  uint8_t* h_stage = nullptr;             // pinned, 2 * STAGE_HALF bytes
+  hipEvent_t stage_ev[2]{};
+  hipEvent_t ev[3]{};  // before the copy, after it, after the kernels
+  static constexpr size_t STAGE_HALF = (size_t)8 << 20;
+  sezkp_trace_ingest_info info{};
+  bool have_info = false;
   void release();
 };
 
@@ -440,6 +471,13 @@ struct sezkp_ctx {
   void verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out);
   // full-trace AIR audit of the active trace image (bitmaps: null or (n + 7) / 8 host bytes)
   void air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits);
+  TraceCborBuffers cbor;
+  // TraceFile CBOR bytes (host memory) to step arrays: on the device when the
+  // file is canonical (tv then points into cbor.d_arrays, complete once st is
+  // synchronised, which this call has done), else by the host decoder into
+  // `host` (tv points there; Err SEZKP_E_DECODE with its message). b = 0 in tv.
+  void decode_trace_cbor(const uint8_t* data, size_t len, BlockStore& host, sezkp_trace_view& tv);
+  SEZKP_LOCAL bool decode_trace_cbor_device(const uint8_t* data, size_t len, sezkp_trace_view& tv);
 
   static void* take_spare(std::multimap<size_t, void*>& m, size_t bytes) {
     auto it = m.find(bytes);

@@ -197,6 +197,15 @@ uint64_t manifest_tree_scratch_nodes(uint64_t nblk);
 hipError_t launch_manifest_tree(hipStream_t st, const TraceMetaDev& M, uint64_t nblk, uint32_t* root_a,
                                 uint32_t* root_b);
 
+// TraceFile CBOR bytes in device memory (on a 16-byte boundary) to the four
+// step-major arrays, and the verdict words the host decides on
+// (trace_cbor.hip, trace_cbor_plan.h): mark, scan, compact, parse on st.
+// counts / offs: trace_cbor_tiles(len) words; cand: t words; t >= 1.
+struct TraceCborVerdict;
+hipError_t launch_trace_cbor_decode(hipStream_t st, const uint8_t* d_bytes, uint64_t len, uint64_t steps_off, uint64_t t,
+                                    uint32_t tau, uint32_t* counts, uint64_t* offs, uint64_t* cand, int8_t* input_mv,
+                                    int8_t* mv, uint8_t* has_write, uint16_t* wsym, TraceCborVerdict* verdict);
+
 // Per-row constraint sums of the composition (k_compose_terms): everything
 // of C(i) that does not depend on the transcript, summed over the tapes
 // exactly (integers where they are small, canonical field values otherwise).

@@ -44,6 +44,8 @@ EXPORTS = [
     "sezkp_ctx_trace_blocks", "sezkp_stark_v1_prove_trace", "sezkp_trace_decode_cbor", "sezkp_trace_encode_cbor",
     "sezkp_trace_view_of", "sezkp_trace_free",
     "sezkp_ctx_upload_trace_rows", "sezkp_trace_shard_rows", "sezkp_trace_shard_blocks",
+    "sezkp_ctx_upload_trace_cbor", "sezkp_ctx_decode_trace_cbor", "sezkp_stark_v1_prove_trace_cbor",
+    "sezkp_trace_cbor_head", "sezkp_ctx_trace_ingest_stats",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -88,6 +90,17 @@ class HeadWideInfo(C.Structure):  # sezkp_head_wide_info
     _fields_ = [("col", C.c_uint32), ("tape", C.c_uint32), ("origin", C.c_int64), ("span", C.c_uint32),
                 ("dR", C.c_uint32), ("R", C.c_uint64), ("entries_built", C.c_uint64), ("groups_wide", C.c_uint64),
                 ("groups_fallback", C.c_uint64), ("groups_out_of_span", C.c_uint64), ("table_bytes", C.c_uint64)]
+
+
+# sezkp_trace_ingest_info: path and reason by their SEZKP_INGEST_* values
+INGEST_PATHS = ("device", "host")
+INGEST_REASONS = ("none", "head", "candidates", "step", "chain", "tail", "forced")
+
+
+class TraceIngestInfo(C.Structure):  # sezkp_trace_ingest_info
+    _fields_ = [("path", C.c_uint32), ("reason", C.c_uint32), ("index", C.c_uint64), ("bytes", C.c_uint64),
+                ("t", C.c_uint64), ("tau", C.c_uint32), ("pad", C.c_uint32), ("candidates", C.c_uint64),
+                ("ms_h2d", C.c_double), ("ms_decode", C.c_double), ("ms_host", C.c_double)]
 
 
 class SezkpError(RuntimeError):
@@ -246,6 +259,13 @@ def _load():
     L.sezkp_trace_view_of.restype = C.POINTER(TraceView)
     L.sezkp_trace_view_of.argtypes = [C.c_void_p]
     L.sezkp_trace_free.argtypes = [C.c_void_p]
+    L.sezkp_ctx_upload_trace_cbor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.c_uint32] + E
+    L.sezkp_ctx_decode_trace_cbor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)] + E
+    L.sezkp_stark_v1_prove_trace_cbor.argtypes = [C.c_void_p, C.c_size_t, C.c_uint32, C.c_uint32, C.POINTER(Buf),
+                                                  C.c_char_p] + E
+    L.sezkp_trace_cbor_head.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
+                                        C.POINTER(C.c_uint64)]
+    L.sezkp_ctx_trace_ingest_stats.argtypes = [C.c_void_p, C.POINTER(TraceIngestInfo)]
     return L
 
 

@@ -11,10 +11,11 @@ import json
 import struct
 from dataclasses import dataclass, field
 
-from ._lib import (AIR_FAMILIES, SEZKP_FLAG_ROOT_FROM_TRACE, SEZKP_FLAG_STREAMING, VERIFY_TIMES, AirAuditC, Buf,
-                   ProofRef, SezkpError, VerifyResultC, check, lib, take_buf)
+from ._lib import (AIR_FAMILIES, INGEST_PATHS, INGEST_REASONS, SEZKP_FLAG_ROOT_FROM_TRACE, SEZKP_FLAG_STREAMING,
+                   VERIFY_TIMES, AirAuditC, Buf, ProofRef, SezkpError, TraceIngestInfo, VerifyResultC, check, lib,
+                   take_buf)
 from .blocks import BlockSoA
-from .trace import trace_view
+from .trace import Trace, cbor_bytes, trace_view
 
 STAGES = ["expand", "col_commit", "col_outer", "compose", "intt", "lde_ntt", "deep", "layer0_tree",
           "layer0_upper", "fri_fold_trees", "col_openings", "fri_paths", "total",
@@ -207,6 +208,22 @@ class StarkV1:
         return ProofArtifact("stark", root.raw, proof, _meta(proof, int(v.tau), streaming))
 
     @staticmethod
+    def prove_trace_cbor(data, b: int, streaming: bool = False) -> ProofArtifact:
+        """prove_trace from a TraceFile's CBOR bytes, decoded on the device
+        (sezkp_stark_v1_prove_trace_cbor)."""
+        p, n, _keep = cbor_bytes(data)
+        if not 0 <= int(b) < 1 << 32:
+            raise SezkpError(-1, "trace: b must fit 32 bits")
+        pb = Buf()
+        root = C.create_string_buffer(32)
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_stark_v1_prove_trace_cbor(p, n, int(b), SEZKP_FLAG_STREAMING if streaming else 0, C.byref(pb),
+                                                  root, err, 1024), err)
+        proof = take_buf(pb)
+        tau = int.from_bytes(proof[8:16], "little")  # the proof's header: domain_n, tau
+        return ProofArtifact("stark", root.raw, proof, _meta(proof, tau, streaming))
+
+    @staticmethod
     def verify(artifact: ProofArtifact, blocks: BlockSoA, manifest_root: bytes) -> None:
         """StarkV1::verify (lib.rs:144-162 -> v1/verify.rs:60-196), host CPU."""
         if artifact.backend != "stark":
@@ -274,6 +291,45 @@ class ProverContext:
         self.tau, self.n_rows = int(v.tau), int(v.t)
         self.n_blocks = -(-int(v.t) // int(v.b))
         del keep  # the call is synchronous
+
+    def upload_trace_cbor(self, data, b: int) -> None:
+        """Upload a TraceFile from its CBOR bytes: the device decodes a
+        canonical file (a declined one goes through the host decoder, with the
+        same result), then partitions it as upload_trace does
+        (sezkp_ctx_upload_trace_cbor). `data`: see trace.cbor_bytes."""
+        p, n, keep = cbor_bytes(data)
+        if not 0 <= int(b) < 1 << 32:
+            raise SezkpError(-1, "trace: b must fit 32 bits")
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_upload_trace_cbor(self._h, p, n, int(b), err, 1024), err)
+        st = self.trace_ingest_stats()
+        self.tau, self.n_rows = st["tau"], st["t"]
+        self.n_blocks = -(-st["t"] // int(b))
+        del keep  # the call is synchronous
+
+    def decode_trace_cbor(self, data) -> Trace:
+        """The decode of upload_trace_cbor alone, read back into a Trace
+        (sezkp_ctx_decode_trace_cbor); the context's trace image is untouched."""
+        p, n, keep = cbor_bytes(data)
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_decode_trace_cbor(self._h, p, n, C.byref(h), err, 1024), err)
+        del keep
+        return Trace._take(h)
+
+    def trace_ingest_stats(self) -> dict:
+        """What the last upload_trace_cbor / decode_trace_cbor call did
+        (sezkp_ctx_trace_ingest_stats): path "device" or "host", the reason the
+        device path declined ("none" when it did not) with the step index of
+        "step" / "chain", bytes, t, tau, candidates, and the times ms_h2d,
+        ms_decode (HIP events) and ms_host."""
+        i = TraceIngestInfo()
+        rc = lib.sezkp_ctx_trace_ingest_stats(self._h, C.byref(i))
+        if rc != 0:
+            raise SezkpError(rc, "trace_ingest_stats: no decode call on this context yet, or a proof is in flight")
+        return {"path": INGEST_PATHS[i.path], "reason": INGEST_REASONS[i.reason], "index": int(i.index),
+                "bytes": int(i.bytes), "t": int(i.t), "tau": int(i.tau), "candidates": int(i.candidates),
+                "ms_h2d": i.ms_h2d, "ms_decode": i.ms_decode, "ms_host": i.ms_host}
 
     def upload_trace_rows(self, input_mv, mv, has_write, wsym, b: int, t: int, row0: int) -> None:
         """upload_trace from arrays that hold only rows [row0, row0 + len) of a

@@ -27,8 +27,10 @@ From the movement log itself (`sezkp-cli prove --trace` over several GPUs):
     python -m sezkp_amd.launch prove --trace trace.cbor --b B --out proof.cbor \\
         [--out-manifest M] [--manifest M] [--gpus P] [--comm rccl|host]
 
-Every rank decodes the TraceFile and uploads only the rows it reads
-(`upload_trace_rows`); the ranks partition their own blocks on their GPUs
+Every rank sends the TraceFile's bytes to its GPU, which decodes them and
+keeps only the rows the rank reads (`upload_trace_cbor`; a file the device
+decoder declines is decoded on the host, with the same result); the ranks
+partition their own blocks on their GPUs
 and commit the manifest together in the proof. Rank 0 writes the artifact
 and, with --out-manifest, the manifest `sezkp-cli commit` gives for the
 partitioned blocks. --manifest is compared with the root the GPUs computed
@@ -110,19 +112,19 @@ def _trace_outputs(args, ctx, art) -> None:
 
 
 def _trace_worker(rank: int, world: int, port: int, args, q) -> None:
-    """`prove --trace` on one rank: decode the TraceFile, upload only this
-    rank's rows (upload_trace_rows), prove without a root; rank 0 writes."""
+    """`prove --trace` on one rank: the TraceFile's bytes go to the rank's GPU,
+    which decodes the whole file and keeps the rows the rank reads
+    (upload_trace_cbor); prove without a root; rank 0 writes."""
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import torch.distributed as dist
     dist.init_process_group("gloo", rank=rank, world_size=world)
     try:
-        from . import ShardedProverContext, Trace, trace_shard_rows
+        from . import ShardedProverContext
         t0 = time.perf_counter()
-        tr = Trace.from_cbor(open(args.trace, "rb").read())
-        row0, nrows = trace_shard_rows(tr.t, args.b, rank, world)
-        t_load = time.perf_counter() - t0
+        raw = open(args.trace, "rb").read()
         ctx = ShardedProverContext(rank, world, device=0 if args.comm == "host" else rank, comm=args.comm)
-        ctx.upload_trace_rows(*(a[row0:row0 + nrows] for a in tr.arrays()), args.b, tr.t, row0)
+        ctx.upload_trace_cbor(raw, args.b)
+        t_load = time.perf_counter() - t0
         t1 = time.perf_counter()
         art = ctx.prove(streaming=args.stream)
         t_prove = time.perf_counter() - t1
@@ -236,11 +238,11 @@ def prove(args) -> int:
         print("error: prove takes --blocks and --manifest, or --trace and --b", file=sys.stderr)
         return 2
     if args.trace and args.gpus == 1 and args.comm == "rccl":
-        from . import ProverContext, Trace
+        from . import ProverContext
         try:
-            tr = Trace.from_cbor(open(args.trace, "rb").read())
+            raw = open(args.trace, "rb").read()
             ctx = ProverContext(0)
-            ctx.upload_trace(*tr.arrays(), args.b)
+            ctx.upload_trace_cbor(raw, args.b)
             art = ctx.prove(streaming=args.stream)
             _trace_outputs(args, ctx, art)
         except Exception as e:

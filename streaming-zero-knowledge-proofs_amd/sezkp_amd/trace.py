@@ -125,6 +125,11 @@ class Trace:
         rc = lib.sezkp_trace_decode_cbor(data, len(data), C.byref(h), err, 512)
         if rc != 0:
             raise SezkpError(rc, err.value.decode())
+        return cls._take(h)
+
+    @classmethod
+    def _take(cls, h) -> "Trace":
+        """The arrays of a sezkp_trace handle, which is freed."""
         try:
             v = lib.sezkp_trace_view_of(h).contents
             t, tau = int(v.t), int(v.tau)
@@ -146,3 +151,31 @@ class Trace:
         if rc != 0:
             raise SezkpError(rc, "encode trace cbor")
         return take_buf(b)
+
+
+def cbor_bytes(data):
+    """(address, length, keep) of a TraceFile's CBOR bytes for the C ABI: bytes
+    / bytearray / memoryview / a numpy uint8 array, or a CPU torch uint8
+    tensor (a pinned one is copied to the device without staging)."""
+    if _is_torch(data):
+        if data.is_cuda or data.element_size() != 1 or not data.is_contiguous():
+            raise SezkpError(-1, "trace bytes: a contiguous CPU uint8 tensor is needed")
+        return (data.data_ptr() if data.numel() else None), int(data.numel()), data
+    if isinstance(data, (bytes, bytearray, memoryview)):
+        a = np.frombuffer(data, dtype=np.uint8)
+    else:
+        a = np.ascontiguousarray(data, dtype=np.uint8).reshape(-1)
+    # an empty file is still a file: a non-null address, so that it is the
+    # decoder that answers
+    keep = a if a.size else np.zeros(1, np.uint8)
+    return keep.ctypes.data, int(a.size), keep
+
+
+def trace_cbor_head(data):
+    """(t, tau, steps_off) when the bytes start with the canonical TraceFile
+    head the device decoder takes, else None (sezkp_trace_cbor_head)."""
+    p, n, _keep = cbor_bytes(data)
+    t, tau, off = C.c_uint64(), C.c_uint32(), C.c_uint64()
+    if not lib.sezkp_trace_cbor_head(p, n, C.byref(t), C.byref(tau), C.byref(off)):
+        return None
+    return t.value, tau.value, off.value
