@@ -12,7 +12,7 @@
 
 #include "prover_ctx.h"
 
-// Full-trace AIR audit (sezkp_stark.h; semantics at k_air_audit, trace.hip):
+// Full-trace AIR audit (sezkp_stark.h; semantics at k_air_audit, air_rows.hip):
 // air.rs:49-136 on every (row, tape) cell, and the rows the verifier's
 // opened-row check (verify.rs:156-182) would reject, with the alpha reuse of
 // prover.rs:86-98 (one boundary family). The derived columns (row -> block,

@@ -10,7 +10,7 @@
 //  * leaf_hash and merkle_root of the manifest (crates/sezkp-merkle/src/
 //    lib.rs:85-117, 140-157): a plain BLAKE3 over the block's fields, parents
 //    BLAKE3(l || r) with odd promotion.
-// k_expand (trace.hip) has already written the block-local heads and their
+// k_expand (trace_image.hip) has already written the block-local heads and their
 // per-block range (TraceDev::head, head_rng); the layouts host and device
 // share are in trace_plan.h.
 //

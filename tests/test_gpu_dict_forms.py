@@ -1,6 +1,6 @@
 """GPU parity of the dictionary commitment's large-shape forms at 2^16 and 2^17 rows.
 
-`make_plan` (csrc/trace.hip) gives a commit lane 2^(6 + a) rows, and `a` > 0
+`make_plan` (csrc/dict_commit.hip) gives a commit lane 2^(6 + a) rows, and `a` > 0
 needs a device with 2^21 rows or more, so below that only the `a` = 0 forms of
 `dict_lane`, `k_col_commit_dict` and `k_col_open` run. The test hook
 `SEZKP_TEST_DICT_PLAN_ROWS_LOG=<v>` makes the planner choose K and `a` as on a
@@ -97,7 +97,7 @@ REQUIRED = (
 
 
 def model_plan(lo, hi, mv_range, n, nrows, cap=DICT_CAP):
-    """make_plan (csrc/trace.hip) restated line by line: the plan of a column
+    """make_plan (csrc/dict_commit.hip) restated line by line: the plan of a column
     with values in [lo, hi] (mv_range: the tape's move range, head columns
     only). Not an independent check of K and a (the ladder is); it supplies
     the expected R, dR and min."""

@@ -444,9 +444,9 @@ def test_prove_random_shapes_one_context(gpu_ok, product, oracle):
     ctx.close()
 
 
-@pytest.mark.parametrize("rows", ["1", "2"])
+@pytest.mark.parametrize("rows", ["1", "2", "4"])
 def test_compose_rows_per_lane_bit_exact(gpu_ok, product, oracle, monkeypatch, rows):
-    """The composition kernel with 1 and 2 (default) rows per lane, on a
+    """The composition kernel with 1, 2 (default) and 4 rows per lane, on a
     trace with ragged blocks (first/last rows inside a lane's group)."""
     monkeypatch.setenv("SEZKP_COMPOSE_ROWS", rows)
     blocks = product.synthetic_blocks(1 << 13, 333, 5, 31)

@@ -1,4 +1,4 @@
-"""GPU parity of the piecewise columns' U tables keyed by value (trace.hip,
+"""GPU parity of the piecewise columns' U tables keyed by value (col_commit.hip,
 k_col_tables / pw_unit).
 
 A per-block column (win_len, in_off, out_off) whose signed range over the
