@@ -401,9 +401,9 @@ void sezkp_trace_free(sezkp_trace* t);
  * decode message is the host decoder's), the same arrays (wsym = 0 where
  * there is no write).
  * SEZKP_TRACE_CBOR_HOST=1 (read per call) forces the host decoder.
- * Out of scope: blocks.cbor and JSONL block files on the device (their step
- * records are the same), a staged, pipelined form, input bytes that are
- * already in device memory, JSON traces. */
+ * Out of scope: JSONL block files on the device, a staged, pipelined form,
+ * input bytes that are already in device memory, JSON traces. (Block files as
+ * CBOR: see "block files decoded on the device" below.) */
 /* Decode, then upload as sezkp_ctx_upload_trace does with block size b. A null
  * ctx, data or b = 0: SEZKP_E_INVALID before any device call. len = 0 with a
  * non-null data is an empty file, not a bad argument: the decoder refuses it
@@ -457,6 +457,93 @@ typedef struct sezkp_trace_ingest_info {
 /* SEZKP_OK, or SEZKP_E_INVALID for a null argument, while a proof is in
  * flight, or before the context's first decode call. */
 int32_t sezkp_ctx_trace_ingest_stats(const sezkp_ctx* ctx, sezkp_trace_ingest_info* out);
+
+/* ------------------------------------------------ block files decoded on the device
+ * sezkp_blocks_decode_cbor is a single-threaded pull parser over the whole of
+ * blocks.cbor (Vec<BlockSummary>, sezkp-core io.rs:57-65), on the host in front
+ * of the first kernel. These take the file's bytes (host memory, pinned or
+ * pageable) and decode them on the context's GPU: the four step arrays stay
+ * in device memory and never visit the host; only the block fields come home.
+ * The device path takes exactly the canonical form ciborium and
+ * sezkp_blocks_encode_cbor write (csrc/blocks_cbor_plan.h):
+ *   array(B), B >= 1, of
+ *   AE | 67 "version" uint<=u16 | 68 "block_id" uint<=u32 | 67 "step_lo" uint | 67 "step_hi" uint |
+ *   67 "ctrl_in" uint<=u16 | 68 "ctrl_out" uint<=u16 | 6A "in_head_in" int | 6B "in_head_out" int |
+ *   67 "windows" array(tau) x (A2 | 64 "left" int | 65 "right" int) |
+ *   6F "head_in_offsets" array(tau) x uint<=u32 | 70 "head_out_offsets" array(tau) x uint<=u32 |
+ *   6C "movement_log" | A1 | 65 "steps" | array(n_k), n_k >= 1, of step records (as in a trace file) |
+ *   68 "pre_tags" array(tau) x (90 | 16 x uint<=255) | 69 "post_tags" the same,
+ * the last block ending at len, every integer in its minimal-length head and
+ * inside its field's type, tau <= 255. It declines anything else, and a
+ * declined call runs sezkp_blocks_decode_cbor's decoder on the host. For every
+ * input the result is what sezkp_blocks_decode_cbor followed by
+ * sezkp_ctx_upload gives: the same code, the same message (every decode
+ * message is the host decoder's), the same arrays, the same proof bytes.
+ * SEZKP_BLOCKS_CBOR_HOST=1 (read per call) forces the host decoder.
+ * Out of scope: JSONL block files on the device, the ingest of the commands
+ * that upload nothing (commit, verify-commit, verify), a staged, pipelined
+ * form, input bytes that are already in device memory, the launcher.
+ *
+ * A null ctx or data: SEZKP_E_INVALID before any device call. len = 0 with a
+ * non-null data is an empty file: the decoder refuses it as
+ * sezkp_blocks_decode_cbor does. A decode failure: SEZKP_E_DECODE with the host
+ * decoder's message, the context's trace state untouched. */
+/* Decode and keep: the step arrays stay in the context's ingest buffers (on
+ * the device, or on the host when the device path declined) as the context's
+ * pending ingest. *meta_out (may be null; free with sezkp_blocks_free): every
+ * block field and step_start, the four step-array pointers of its view NULL.
+ * The pending ingest is dropped by the sezkp_ctx_upload_ingested that consumes
+ * it, by the next ingest or device decode, and by sezkp_ctx_destroy. */
+int32_t sezkp_ctx_ingest_blocks_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, sezkp_blocks** meta_out, char* err,
+                                     size_t err_len);
+/* sezkp_ctx_upload of the pending ingest (its failures and their wording);
+ * SEZKP_E_INVALID when none is pending. On a sharded context only the rows of
+ * the rank's blocks are copied into the image. */
+int32_t sezkp_ctx_upload_ingested(sezkp_ctx* ctx, char* err, size_t err_len);
+/* The two in one call. */
+int32_t sezkp_ctx_upload_blocks_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, char* err, size_t err_len);
+/* The same decode, with everything read back into a host handle (free with
+ * sezkp_blocks_free). Needs no uploaded trace and leaves the context's trace
+ * state untouched (a pending ingest is dropped): the parity entry point. */
+int32_t sezkp_ctx_decode_blocks_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, sezkp_blocks** out, char* err,
+                                     size_t err_len);
+/* Stateless, device 0: decode + sezkp_stark_v1_prove. Null arguments are
+ * answered before any device is touched, and so is a file without a canonical
+ * head that the host decoder refuses. */
+int32_t sezkp_stark_v1_prove_blocks_cbor(const uint8_t* data, size_t len, const uint8_t manifest_root[32], uint32_t flags,
+                                         sezkp_buf* proof_bytes, char* err, size_t err_len);
+/* Host only: 1 and *n_blocks, *tau, *first_off (the offset of block 0) when
+ * the bytes start with array(B), B >= 1, and a canonical head of block 0, and
+ * B blocks can fit in the rest of the file, else 0 (also for a null argument). */
+int32_t sezkp_blocks_cbor_head(const uint8_t* data, size_t len, uint32_t* n_blocks, uint32_t* tau, uint64_t* first_off);
+/* What the last ingest / upload_blocks_cbor / decode_blocks_cbor call of the
+ * context did (path: SEZKP_INGEST_DEVICE / SEZKP_INGEST_HOST). */
+#define SEZKP_BLOCKS_R_NONE 0u              /* the device path decoded the file */
+#define SEZKP_BLOCKS_R_HEAD 1u              /* no canonical head */
+#define SEZKP_BLOCKS_R_BLOCK_CANDIDATES 2u  /* fewer than B block signatures */
+#define SEZKP_BLOCKS_R_STEP_CANDIDATES 3u   /* fewer step signatures than the blocks' heads count steps */
+#define SEZKP_BLOCKS_R_BLOCK_HEAD 4u        /* block `index`'s head is not canonical (block 0: or not behind the array head) */
+#define SEZKP_BLOCKS_R_STEP 5u              /* step `index` is not a canonical record */
+#define SEZKP_BLOCKS_R_CHAIN 6u             /* step `index` does not start where its block's head or step index - 1 ends */
+#define SEZKP_BLOCKS_R_BLOCK_TAIL 7u        /* block `index`'s tail is not canonical or does not end at the next block / at len */
+#define SEZKP_BLOCKS_R_FORCED 8u            /* SEZKP_BLOCKS_CBOR_HOST=1 */
+typedef struct sezkp_blocks_ingest_info {
+  uint32_t path;
+  uint32_t reason;           /* SEZKP_BLOCKS_R_*: why the device path declined */
+  uint64_t index;            /* the block or step of the reason, else 0 */
+  uint64_t bytes;            /* len */
+  uint32_t n_blocks;         /* blocks, steps and tapes of what was decoded, on either path; of a file that */
+  uint32_t tau;              /* was refused, those of its head (0 without a canonical head; t 0) */
+  uint64_t t;
+  uint64_t block_candidates; /* signatures found (0 when the device did not look) */
+  uint64_t step_candidates;
+  double ms_h2d;             /* HIP events: the bytes' copy, the kernels; 0 when not run */
+  double ms_decode;
+  double ms_host;            /* the host decoder's wall time; 0 when it did not run */
+} sezkp_blocks_ingest_info;
+/* SEZKP_OK, or SEZKP_E_INVALID for a null argument, while a proof is in
+ * flight, or before the context's first decode call. */
+int32_t sezkp_ctx_blocks_ingest_stats(const sezkp_ctx* ctx, sezkp_blocks_ingest_info* out);
 
 /* ------------------------------------------------ full-trace AIR audit
  * Does the committed trace satisfy the AIR, on every row? The reference

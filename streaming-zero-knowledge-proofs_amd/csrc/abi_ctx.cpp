@@ -650,4 +650,120 @@ int32_t sezkp_stark_v1_prove_trace_cbor(const uint8_t* data, size_t len, uint32_
   return rc;
 }
 
+// ---- block files decoded on the device (ctx_blocks_cbor.cpp)
+// the block fields and step_start of a decoded store as a handle without steps
+static sezkp_blocks* blocks_meta_handle(const BlockStore& src) {
+  std::unique_ptr<sezkp_blocks> b(new sezkp_blocks());
+  BlockStore& s = b->s;
+  s.tau = src.tau;
+  s.version = src.version;
+  s.block_id = src.block_id;
+  s.step_lo = src.step_lo;
+  s.step_hi = src.step_hi;
+  s.ctrl_in = src.ctrl_in;
+  s.ctrl_out = src.ctrl_out;
+  s.in_head_in = src.in_head_in;
+  s.in_head_out = src.in_head_out;
+  s.win_left = src.win_left;
+  s.win_right = src.win_right;
+  s.off_in = src.off_in;
+  s.off_out = src.off_out;
+  s.step_start = src.step_start;
+  s.bind();
+  s.view.input_mv = nullptr;
+  s.view.mv = nullptr;
+  s.view.has_write = nullptr;
+  s.view.wsym = nullptr;
+  return b.release();
+}
+
+int32_t sezkp_ctx_ingest_blocks_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, sezkp_blocks** meta_out, char* err,
+                                     size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !data) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->ingest_blocks_cbor(data, len);
+    if (meta_out) *meta_out = blocks_meta_handle(ctx->bcbor.pend);
+  });
+}
+
+int32_t sezkp_ctx_upload_ingested(sezkp_ctx* ctx, char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->upload_ingested();
+  });
+}
+
+int32_t sezkp_ctx_upload_blocks_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !data) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->ingest_blocks_cbor(data, len);
+    ctx->upload_ingested();
+  });
+}
+
+int32_t sezkp_ctx_decode_blocks_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, sezkp_blocks** out, char* err,
+                                     size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !data || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    std::unique_ptr<sezkp_blocks> b(new sezkp_blocks());
+    sezkp_block_view steps{};
+    ctx->decode_blocks_cbor(data, len, b->s, steps);
+    if (ctx->bcbor.info.path == SEZKP_INGEST_DEVICE) {
+      BlockStore& s = b->s;
+      const size_t t = (size_t)ctx->bcbor.info.t, cells = t * s.tau;
+      s.input_mv.resize(t);
+      s.mv.resize(cells);
+      s.has_write.resize(cells);
+      s.wsym.resize(cells);
+      auto get = [&](void* dst, const void* src, size_t bytes) {
+        if (bytes) HIP_OR_THROW(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, ctx->st));
+      };
+      get(s.input_mv.data(), steps.input_mv, t);
+      get(s.mv.data(), steps.mv, cells);
+      get(s.has_write.data(), steps.has_write, cells);
+      get(s.wsym.data(), steps.wsym, cells * 2);
+      HIP_OR_THROW(hipStreamSynchronize(ctx->st));
+    }
+    b->s.bind();
+    *out = b.release();
+  });
+}
+
+int32_t sezkp_ctx_blocks_ingest_stats(const sezkp_ctx* cctx, sezkp_blocks_ingest_info* out) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || !out || ctx->busy() || !ctx->bcbor.have_info) return SEZKP_E_INVALID;
+  *out = ctx->bcbor.info;
+  return SEZKP_OK;
+}
+
+// The argument checks come before any device is touched. A file without the
+// canonical head would be decoded on the host anyway: it is decoded here,
+// once, before a device is opened (so its refusal needs none), and its blocks
+// are uploaded as sezkp_stark_v1_prove uploads them.
+int32_t sezkp_stark_v1_prove_blocks_cbor(const uint8_t* data, size_t len, const uint8_t manifest_root[32], uint32_t flags,
+                                         sezkp_buf* proof_bytes, char* err, size_t err_len) {
+  BlockStore host;
+  bool decoded = false;
+  const int32_t pre = guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!data || !manifest_root || !proof_bytes) throw Err{SEZKP_E_INVALID, "null argument"};
+    BlocksCborHead h;
+    if (blocks_cbor_head(CborSpan{data, len}, h)) return;
+    std::string e;
+    if (!decode_blocks_cbor(data, len, host, e)) throw Err{SEZKP_E_DECODE, e};
+    decoded = true;
+  });
+  if (pre != SEZKP_OK) return pre;
+  sezkp_ctx* ctx = sezkp_ctx_create(0, err, err_len);
+  if (!ctx) return SEZKP_E_DEVICE;
+  int32_t rc = decoded ? sezkp_ctx_upload(ctx, &host.view, err, err_len)
+                       : sezkp_ctx_upload_blocks_cbor(ctx, data, len, err, err_len);
+  if (rc == SEZKP_OK) rc = sezkp_ctx_prove(ctx, manifest_root, flags, proof_bytes, err, err_len);
+  sezkp_ctx_destroy(ctx);
+  return rc;
+}
+
 }  // extern "C"

@@ -12,6 +12,7 @@
 #include "abi_util.h"
 #include "codec.h"
 #include "host_crypto.h"
+#include "blocks_cbor_plan.h"
 #include "trace_cbor_plan.h"
 #include "trace_plan.h"
 
@@ -100,6 +101,15 @@ int32_t sezkp_trace_cbor_head(const uint8_t* data, size_t len, uint64_t* t, uint
   *t = h.t;
   *tau = h.tau;
   *steps_off = h.steps_off;
+  return 1;
+}
+// the canonical head of a block file the device decoder takes (blocks_cbor_plan.h)
+int32_t sezkp_blocks_cbor_head(const uint8_t* data, size_t len, uint32_t* n_blocks, uint32_t* tau, uint64_t* first_off) {
+  BlocksCborHead h;
+  if (!data || !n_blocks || !tau || !first_off || !blocks_cbor_head(CborSpan{data, len}, h)) return 0;
+  *n_blocks = h.n_blocks;
+  *tau = h.tau;
+  *first_off = h.first_off;
   return 1;
 }
 const sezkp_trace_view* sezkp_trace_view_of(const sezkp_trace* t) { return t ? &t->view : nullptr; }

@@ -238,6 +238,7 @@ sezkp_ctx::~sezkp_ctx() {
   audit.release();
   vfy.release();
   cbor.release();
+  bcbor.release();
   dict.release();
   for (auto& e : ev)
     if (e) (void)hipEventDestroy(e);

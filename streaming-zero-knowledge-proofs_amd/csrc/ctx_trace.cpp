@@ -378,14 +378,20 @@ void sezkp_ctx::write_trace(TraceSlot& t, const sezkp_block_view& v, hipStream_t
   auto cp = [&](void* dst, const void* src, size_t bytes) {
     copy_chunked(dst, src, bytes, COPY_CHUNK, hipMemcpyHostToDevice, s);
   };
+  // a step array may lie in device memory (a block file decoded there): the kind per array
+  auto cp_steps = [&](void* dst, const void* src, size_t bytes) {
+    if (!bytes) return;
+    const bool dev = on_device(src, device);
+    copy_chunked(dst, src, bytes, dev ? bytes : COPY_CHUNK, dev ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s);
+  };
   uint16_t* raw_ws = reinterpret_cast<uint16_t*>(t.raw);
   int8_t* raw_mv = reinterpret_cast<int8_t*>(t.raw + 2 * cells);
   uint8_t* raw_hw = t.raw + 3 * cells;
   const size_t c0 = (size_t)row0 * tau, nc = (size_t)nrows * tau;
-  cp(raw_ws + c0, v.wsym, nc * 2);
-  cp(raw_mv + c0, v.mv, nc);
-  cp(raw_hw + c0, v.has_write, nc);
-  cp(t.imv + row0, v.input_mv, nrows);
+  cp_steps(raw_ws + c0, v.wsym, nc * 2);
+  cp_steps(raw_mv + c0, v.mv, nc);
+  cp_steps(raw_hw + c0, v.has_write, nc);
+  cp_steps(t.imv + row0, v.input_mv, nrows);
   cp(t.bw, t.h_tab, 3 * nt * 8);
   if (staged_copy) t.image_pending = true;
   else launch_image(t, s, row0, nrows);

@@ -25,23 +25,18 @@ void TraceCborBuffers::release() {
     if (e) (void)hipEventDestroy(e);
   *this = TraceCborBuffers{};
 }
+void cbor_grow(void** p, size_t& cap, size_t bytes) {
+  if (*p && bytes <= cap) return;
+  if (*p) (void)hipFree(*p);
+  *p = nullptr;
+  cap = 0;
+  const size_t want = bytes + bytes / 4 + 64;
+  HIP_OR_THROW(hipMalloc(p, want));
+  cap = want;
+}
 }  // namespace sezkp::detail
 
 namespace {
-// a device block of at least `bytes` bytes: kept when large enough, else
-// replaced by one a quarter larger than asked for (contents undefined)
-template <class Tp>
-void grow(Tp*& p, size_t& cap, size_t bytes) {
-  if (p && bytes <= cap) return;
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  cap = 0;
-  const size_t want = bytes + bytes / 4 + 64;
-  void* q = nullptr;
-  HIP_OR_THROW(hipMalloc(&q, want));
-  p = static_cast<Tp*>(q);
-  cap = want;
-}
 // page-locked host memory the runtime knows (hipHostMalloc, hipHostRegister):
 // copied from directly; anything else goes through the staging block
 bool host_pinned(const void* p) {
@@ -53,6 +48,35 @@ bool host_pinned(const void* p) {
   return a.type == hipMemoryTypeHost;
 }
 }  // namespace
+
+void sezkp_ctx::cbor_bytes_to_device(const uint8_t* data, size_t len) {
+  for (auto& e : cbor.ev)
+    if (!e) HIP_OR_THROW(hipEventCreate(&e));
+  cbor_grow(cbor.d_bytes, cbor.bytes_cap, len);
+  // ---- the bytes: straight from pinned memory, else through the staging block
+  HIP_OR_THROW(hipEventRecord(cbor.ev[0], st));
+  if (host_pinned(data)) {
+    copy_chunked(cbor.d_bytes, data, len, COPY_CHUNK, hipMemcpyHostToDevice, st);
+  } else {
+    constexpr size_t H = TraceCborBuffers::STAGE_HALF;
+    if (!cbor.h_stage) {
+      void* q = nullptr;
+      HIP_OR_THROW(hipHostMalloc(&q, 2 * H, hipHostMallocDefault));
+      cbor.h_stage = static_cast<uint8_t*>(q);
+      for (auto& e : cbor.stage_ev) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+    }
+    size_t k = 0;
+    for (size_t o = 0; o < len; k++) {
+      const size_t n = std::min(H, len - o), half = k & 1;
+      if (k >= 2) HIP_OR_THROW(hipEventSynchronize(cbor.stage_ev[half]));  // the half's previous copy
+      memcpy(cbor.h_stage + half * H, data + o, n);
+      HIP_OR_THROW(hipMemcpyAsync(cbor.d_bytes + o, cbor.h_stage + half * H, n, hipMemcpyHostToDevice, st));
+      HIP_OR_THROW(hipEventRecord(cbor.stage_ev[half], st));
+      o += n;
+    }
+  }
+  HIP_OR_THROW(hipEventRecord(cbor.ev[1], st));
+}
 
 // true: the arrays are in cbor.d_arrays (st synchronised), tv points at them.
 // false: declined, cbor.info.reason says why. Throws only for device errors.
@@ -73,18 +97,17 @@ bool sezkp_ctx::decode_trace_cbor_device(const uint8_t* data, size_t len, sezkp_
   const uint64_t t = h.t, cells = t * h.tau;  // t <= len / 18
   uint64_t tail_off = h.steps_off;
   HIP_OR_THROW(hipSetDevice(device));
-  for (auto& e : cbor.ev)
-    if (!e) HIP_OR_THROW(hipEventCreate(&e));
-  // buffers of an earlier call may still be read by the upload it fed
+  // buffers of an earlier call may still be read by the upload it fed; a
+  // pending block-file ingest holds its steps in the same arrays
   HIP_OR_THROW(hipStreamSynchronize(st));
-  grow(cbor.d_arrays, cbor.arrays_cap, (size_t)(4 * cells + t));
+  bcbor.drop_pending();
+  cbor_grow(cbor.d_arrays, cbor.arrays_cap, (size_t)(4 * cells + t));
   uint16_t* d_ws = reinterpret_cast<uint16_t*>(cbor.d_arrays);
   int8_t* d_mv = reinterpret_cast<int8_t*>(cbor.d_arrays + 2 * cells);
   uint8_t* d_hw = cbor.d_arrays + 3 * cells;
   int8_t* d_imv = reinterpret_cast<int8_t*>(cbor.d_arrays + 4 * cells);
   if (t) {
     const size_t ntiles = (size_t)trace_cbor_tiles(len);
-    grow(cbor.d_bytes, cbor.bytes_cap, len);
     if (ntiles > cbor.tiles_cap || !cbor.d_counts) {
       size_t c0 = 0, c1 = 0;
       if (cbor.d_counts) (void)hipFree(cbor.d_counts);
@@ -92,11 +115,11 @@ bool sezkp_ctx::decode_trace_cbor_device(const uint8_t* data, size_t len, sezkp_
       cbor.d_counts = nullptr;
       cbor.d_offs = nullptr;
       cbor.tiles_cap = 0;
-      grow(cbor.d_counts, c0, ntiles * 4);
-      grow(cbor.d_offs, c1, ntiles * 8);
+      cbor_grow(cbor.d_counts, c0, ntiles * 4);
+      cbor_grow(cbor.d_offs, c1, ntiles * 8);
       cbor.tiles_cap = ntiles;
     }
-    grow(cbor.d_cand, cbor.cand_cap, (size_t)t * 8);
+    cbor_grow(cbor.d_cand, cbor.cand_cap, (size_t)t * 8);
     if (!cbor.d_verdict) {
       void* q = nullptr;
       HIP_OR_THROW(hipMalloc(&q, sizeof(TraceCborVerdict)));
@@ -104,29 +127,7 @@ bool sezkp_ctx::decode_trace_cbor_device(const uint8_t* data, size_t len, sezkp_
       HIP_OR_THROW(hipHostMalloc(&q, sizeof(TraceCborVerdict), hipHostMallocDefault));
       cbor.h_verdict = static_cast<TraceCborVerdict*>(q);
     }
-    // ---- the bytes: straight from pinned memory, else through the staging block
-    HIP_OR_THROW(hipEventRecord(cbor.ev[0], st));
-    if (host_pinned(data)) {
-      copy_chunked(cbor.d_bytes, data, len, COPY_CHUNK, hipMemcpyHostToDevice, st);
-    } else {
-      constexpr size_t H = TraceCborBuffers::STAGE_HALF;
-      if (!cbor.h_stage) {
-        void* q = nullptr;
-        HIP_OR_THROW(hipHostMalloc(&q, 2 * H, hipHostMallocDefault));
-        cbor.h_stage = static_cast<uint8_t*>(q);
-        for (auto& e : cbor.stage_ev) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-      }
-      size_t k = 0;
-      for (size_t o = 0; o < len; k++) {
-        const size_t n = std::min(H, len - o), half = k & 1;
-        if (k >= 2) HIP_OR_THROW(hipEventSynchronize(cbor.stage_ev[half]));  // the half's previous copy
-        memcpy(cbor.h_stage + half * H, data + o, n);
-        HIP_OR_THROW(hipMemcpyAsync(cbor.d_bytes + o, cbor.h_stage + half * H, n, hipMemcpyHostToDevice, st));
-        HIP_OR_THROW(hipEventRecord(cbor.stage_ev[half], st));
-        o += n;
-      }
-    }
-    HIP_OR_THROW(hipEventRecord(cbor.ev[1], st));
+    cbor_bytes_to_device(data, len);
     HIP_OR_THROW(launch_trace_cbor_decode(st, cbor.d_bytes, len, h.steps_off, t, h.tau, cbor.d_counts, cbor.d_offs,
                                           cbor.d_cand, d_imv, d_mv, d_hw, d_ws, cbor.d_verdict));
     HIP_OR_THROW(hipEventRecord(cbor.ev[2], st));

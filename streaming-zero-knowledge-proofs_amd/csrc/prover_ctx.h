@@ -1,6 +1,7 @@
 // prover_ctx.h — the prover context (struct sezkp_ctx) and what its units
 // share: ctx.cpp (life of a context), ctx_upload.cpp, ctx_trace.cpp,
-// ctx_trace_cbor.cpp (trace files decoded on the device), ctx_services.cpp
+// ctx_trace_cbor.cpp and ctx_blocks_cbor.cpp (trace and block files decoded
+// on the device), ctx_services.cpp
 // (audit, batch verify), proof_run.cpp (one proof) and the C ABI in
 // abi_ctx.cpp / abi_kernels.cpp. Internal to the library: nothing
 // outside csrc/ includes it.
@@ -19,6 +20,7 @@
 
 #include "../../include/sezkp_stark.h"
 #include "abi_util.h"
+#include "blocks_cbor_plan.h"
 #include "codec.h"
 #include "comm.h"
 #include "prove_plan.h"
@@ -71,7 +73,8 @@ struct AsyncSlot {
 //   elsewhere:         SEZKP_NO_DICT per upload (upload), SEZKP_FORCE_SHARDED per
 //                      context (ctx_create), SEZKP_VERIFY_CHUNK_BYTES per verify
 //                      call (verify_batch), SEZKP_TRACE_CBOR_HOST per trace-file
-//                      decode (decode_trace_cbor_device)
+//                      decode (decode_trace_cbor_device), SEZKP_BLOCKS_CBOR_HOST per
+//                      block-file decode (decode_blocks_cbor_device)
 struct ProveOptions {
   bool host_trace = false;   // SEZKP_HOST_TRACE=1: host-side marks printed per proof
   bool sync_debug = false;   // SEZKP_SYNC_DEBUG: sync after every launch, to name the failing kernel
@@ -242,6 +245,47 @@ struct TraceCborBuffers {
   bool have_info = false;
   void release();
 };
+
+// Block-file CBOR decoded on the device (sezkp_ctx_ingest_blocks_cbor,
+// ctx_blocks_cbor.cpp). The file's bytes, the step candidates and the decoded
+// step arrays use TraceCborBuffers' blocks (one ingest at a time, of either
+// kind); here is what a block file needs besides: the second kind's tile
+// words, the block candidates, the steps' ends, the block tables and the
+// verdict. `pend`: the ingest that sezkp_ctx_upload_ingested consumes: every
+// block field and step_start on the host, the step arrays in `steps` (device
+// memory after a device decode, else pend's own vectors).
+struct BlocksCborBuffers {
+  uint32_t* d_counts = nullptr;
+  uint64_t* d_offs = nullptr;
+  size_t tiles_cap = 0;  // tiles; the other capacities in bytes
+  uint64_t* d_cand = nullptr;
+  size_t cand_cap = 0;
+  uint64_t* d_ends = nullptr;
+  size_t ends_cap = 0;
+  uint8_t* d_tables = nullptr;
+  size_t tables_cap = 0;
+  BlocksCborVerdict* d_verdict = nullptr;
+  BlocksCborVerdict* h_verdict = nullptr;  // pinned
+  sezkp_blocks_ingest_info info{};
+  bool have_info = false;
+  BlockStore pend;
+  sezkp_block_view steps{};  // input_mv, mv, has_write, wsym of the pending ingest
+  bool pending = false;
+  void drop_pending() {
+    pending = false;
+    pend = BlockStore();
+  }
+  void release();
+};
+// a device block of at least `bytes` bytes: kept when large enough, else
+// replaced by one a quarter larger than asked for (contents undefined)
+void cbor_grow(void** p, size_t& cap, size_t bytes);
+template <class Tp>
+void cbor_grow(Tp*& p, size_t& cap, size_t bytes) {
+  void* q = p;
+  cbor_grow(&q, cap, bytes);
+  p = static_cast<Tp*>(q);
+}
 
 // ---- shared by ctx_upload.cpp and ctx_trace.cpp (defined in ctx_upload.cpp)
 // Blocks of zero steps (step_hi = step_lo - 1, so step_hi - step_lo + 1 wraps
@@ -478,6 +522,20 @@ struct sezkp_ctx {
   // `host` (tv points there; Err SEZKP_E_DECODE with its message). b = 0 in tv.
   void decode_trace_cbor(const uint8_t* data, size_t len, BlockStore& host, sezkp_trace_view& tv);
   SEZKP_LOCAL bool decode_trace_cbor_device(const uint8_t* data, size_t len, sezkp_trace_view& tv);
+  // the file's bytes into cbor.d_bytes on st, straight from pinned memory, else
+  // through the staging block; cbor.ev[0] before the copy, cbor.ev[1] after it
+  SEZKP_LOCAL void cbor_bytes_to_device(const uint8_t* data, size_t len);
+  BlocksCborBuffers bcbor;
+  // Block-file CBOR bytes (host memory) to blocks: on the device when the file
+  // is canonical (the block fields and step_start come home into `out`, whose
+  // step vectors stay empty; `steps` points at the step arrays in
+  // cbor.d_arrays, complete: st is synchronised), else by the host decoder
+  // into `out` (`steps` points there; Err SEZKP_E_DECODE with its message).
+  // Drops a pending ingest.
+  void decode_blocks_cbor(const uint8_t* data, size_t len, BlockStore& out, sezkp_block_view& steps);
+  SEZKP_LOCAL bool decode_blocks_cbor_device(const uint8_t* data, size_t len, BlockStore& out, sezkp_block_view& steps);
+  void ingest_blocks_cbor(const uint8_t* data, size_t len);  // decode into bcbor.pend
+  void upload_ingested();                                    // upload() of the pending ingest, which it drops
 
   static void* take_spare(std::multimap<size_t, void*>& m, size_t bytes) {
     auto it = m.find(bytes);

@@ -69,9 +69,9 @@ __global__ void __launch_bounds__(TC_THREADS) k_cbor_marks(CborSpan s, uint64_t 
   }
 }
 
-// offs[i] = the candidates in the tiles before i; V->candidates = all of them
+// offs[i] = the candidates in the tiles before i; *total = all of them
 __global__ void __launch_bounds__(TC_THREADS) k_cbor_tile_scan(const uint32_t* __restrict__ counts, uint64_t ntiles,
-                                                               uint64_t* __restrict__ offs, TraceCborVerdict* V) {
+                                                               uint64_t* __restrict__ offs, uint64_t* total_out) {
   __shared__ unsigned long long sh[TC_THREADS / 64];
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   constexpr uint32_t PER = TRACE_CBOR_SCAN_PASS / TRACE_CBOR_THREADS;
@@ -110,7 +110,13 @@ __global__ void __launch_bounds__(TC_THREADS) k_cbor_tile_scan(const uint32_t* _
       }
     carry += total;
   }
-  if (threadIdx.x == 0) V->candidates = carry;
+  if (threadIdx.x == 0) *total_out = carry;
+}
+// the scan alone, for blocks_cbor.hip: n counts (candidates per tile, steps
+// per block) to their exclusive scan and, in a device word, their sum
+hipError_t launch_cbor_tile_scan(hipStream_t st, const uint32_t* counts, uint64_t n, uint64_t* offs, uint64_t* total) {
+  hipLaunchKernelGGL(k_cbor_tile_scan, dim3(1), dim3(TC_THREADS), 0, st, counts, n, offs, total);
+  return hipGetLastError();
 }
 
 // Step i from candidate i, and its link: step 0 starts at lo, step i + 1 where
@@ -151,7 +157,7 @@ hipError_t launch_trace_cbor_decode(hipStream_t st, const uint8_t* d_bytes, uint
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_cbor_marks<false>, dim3((uint32_t)ntiles), dim3(TC_THREADS), 0, st, s, steps_off, counts, nullptr,
                      nullptr, t);
-  hipLaunchKernelGGL(k_cbor_tile_scan, dim3(1), dim3(TC_THREADS), 0, st, counts, ntiles, offs, verdict);
+  hipLaunchKernelGGL(k_cbor_tile_scan, dim3(1), dim3(TC_THREADS), 0, st, counts, ntiles, offs, &verdict->candidates);
   hipLaunchKernelGGL(k_cbor_marks<true>, dim3((uint32_t)ntiles), dim3(TC_THREADS), 0, st, s, steps_off, nullptr, offs,
                      cand, t);
   hipLaunchKernelGGL(k_cbor_parse, dim3((uint32_t)pgrid), dim3(TC_THREADS), 0, st, s, steps_off, cand, t, tau, input_mv,

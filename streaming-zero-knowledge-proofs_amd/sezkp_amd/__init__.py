@@ -8,8 +8,8 @@ from ._lib import LIB_PATH, SezkpError, lib  # noqa: F401  (raises ImportError i
 from .backend import (STAGES, AirAudit, ProofArtifact, ProverContext, ShardedProverContext, StarkV1,  # noqa: F401
                       VerifyResult)
 from .blocks import BlockSoA, partition, reference_blocks, reference_trace, simulate, synthetic_blocks  # noqa: F401
-from .trace import Trace, trace_cbor_head, trace_shard_blocks, trace_shard_rows  # noqa: F401
+from .trace import Trace, blocks_cbor_head, trace_cbor_head, trace_shard_blocks, trace_shard_rows  # noqa: F401
 
 __all__ = ["StarkV1", "ProverContext", "ShardedProverContext", "ProofArtifact", "AirAudit", "VerifyResult", "BlockSoA", "Trace", "SezkpError", "simulate", "partition",
-           "trace_shard_rows", "trace_shard_blocks", "trace_cbor_head",
+           "trace_shard_rows", "trace_shard_blocks", "trace_cbor_head", "blocks_cbor_head",
            "synthetic_blocks", "reference_blocks", "reference_trace", "STAGES", "LIB_PATH", "lib"]

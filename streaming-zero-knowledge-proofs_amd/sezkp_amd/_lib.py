@@ -46,6 +46,9 @@ EXPORTS = [
     "sezkp_ctx_upload_trace_rows", "sezkp_trace_shard_rows", "sezkp_trace_shard_blocks",
     "sezkp_ctx_upload_trace_cbor", "sezkp_ctx_decode_trace_cbor", "sezkp_stark_v1_prove_trace_cbor",
     "sezkp_trace_cbor_head", "sezkp_ctx_trace_ingest_stats",
+    "sezkp_ctx_ingest_blocks_cbor", "sezkp_ctx_upload_ingested", "sezkp_ctx_upload_blocks_cbor",
+    "sezkp_ctx_decode_blocks_cbor", "sezkp_stark_v1_prove_blocks_cbor", "sezkp_blocks_cbor_head",
+    "sezkp_ctx_blocks_ingest_stats",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -101,6 +104,18 @@ class TraceIngestInfo(C.Structure):  # sezkp_trace_ingest_info
     _fields_ = [("path", C.c_uint32), ("reason", C.c_uint32), ("index", C.c_uint64), ("bytes", C.c_uint64),
                 ("t", C.c_uint64), ("tau", C.c_uint32), ("pad", C.c_uint32), ("candidates", C.c_uint64),
                 ("ms_h2d", C.c_double), ("ms_decode", C.c_double), ("ms_host", C.c_double)]
+
+
+# sezkp_blocks_ingest_info: the reason by its SEZKP_BLOCKS_R_* value
+BLOCKS_INGEST_REASONS = ("none", "head", "block_candidates", "step_candidates", "block_head", "step", "chain",
+                         "block_tail", "forced")
+
+
+class BlocksIngestInfo(C.Structure):  # sezkp_blocks_ingest_info
+    _fields_ = [("path", C.c_uint32), ("reason", C.c_uint32), ("index", C.c_uint64), ("bytes", C.c_uint64),
+                ("n_blocks", C.c_uint32), ("tau", C.c_uint32), ("t", C.c_uint64), ("block_candidates", C.c_uint64),
+                ("step_candidates", C.c_uint64), ("ms_h2d", C.c_double), ("ms_decode", C.c_double),
+                ("ms_host", C.c_double)]
 
 
 class SezkpError(RuntimeError):
@@ -266,6 +281,15 @@ def _load():
     L.sezkp_trace_cbor_head.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint64), C.POINTER(C.c_uint32),
                                         C.POINTER(C.c_uint64)]
     L.sezkp_ctx_trace_ingest_stats.argtypes = [C.c_void_p, C.POINTER(TraceIngestInfo)]
+    L.sezkp_ctx_ingest_blocks_cbor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)] + E
+    L.sezkp_ctx_upload_ingested.argtypes = [C.c_void_p] + E
+    L.sezkp_ctx_upload_blocks_cbor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t] + E
+    L.sezkp_ctx_decode_blocks_cbor.argtypes = [C.c_void_p, C.c_void_p, C.c_size_t, C.POINTER(C.c_void_p)] + E
+    L.sezkp_stark_v1_prove_blocks_cbor.argtypes = [C.c_void_p, C.c_size_t, C.c_char_p, C.c_uint32,
+                                                   C.POINTER(Buf)] + E
+    L.sezkp_blocks_cbor_head.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
+                                         C.POINTER(C.c_uint64)]
+    L.sezkp_ctx_blocks_ingest_stats.argtypes = [C.c_void_p, C.POINTER(BlocksIngestInfo)]
     return L
 
 

@@ -12,7 +12,7 @@ import struct
 from dataclasses import dataclass, field
 
 from ._lib import (AIR_FAMILIES, INGEST_PATHS, INGEST_REASONS, SEZKP_FLAG_ROOT_FROM_TRACE, SEZKP_FLAG_STREAMING,
-                   VERIFY_TIMES, AirAuditC, Buf, ProofRef, SezkpError, TraceIngestInfo, VerifyResultC, check, lib,
+                   VERIFY_TIMES, AirAuditC, Buf, ProofRef, SezkpError, TraceIngestInfo, BlocksIngestInfo, BLOCKS_INGEST_REASONS, VerifyResultC, check, lib,
                    take_buf)
 from .blocks import BlockSoA
 from .trace import Trace, cbor_bytes, trace_view
@@ -224,6 +224,22 @@ class StarkV1:
         return ProofArtifact("stark", root.raw, proof, _meta(proof, tau, streaming))
 
     @staticmethod
+    def prove_blocks_cbor(data, manifest_root: bytes, streaming: bool = False) -> ProofArtifact:
+        """StarkV1::prove from the CBOR bytes of a block file (blocks.cbor),
+        decoded on the device (sezkp_stark_v1_prove_blocks_cbor)."""
+        p, n, _keep = cbor_bytes(data)
+        root = bytes(manifest_root)
+        if len(root) != 32:
+            raise SezkpError(-1, "manifest_root must be 32 bytes")
+        pb = Buf()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_stark_v1_prove_blocks_cbor(p, n, root, SEZKP_FLAG_STREAMING if streaming else 0, C.byref(pb),
+                                                   err, 1024), err)
+        proof = take_buf(pb)
+        tau = int.from_bytes(proof[8:16], "little")  # the proof's header: domain_n, tau
+        return ProofArtifact("stark", root, proof, _meta(proof, tau, streaming))
+
+    @staticmethod
     def verify(artifact: ProofArtifact, blocks: BlockSoA, manifest_root: bytes) -> None:
         """StarkV1::verify (lib.rs:144-162 -> v1/verify.rs:60-196), host CPU."""
         if artifact.backend != "stark":
@@ -329,6 +345,65 @@ class ProverContext:
             raise SezkpError(rc, "trace_ingest_stats: no decode call on this context yet, or a proof is in flight")
         return {"path": INGEST_PATHS[i.path], "reason": INGEST_REASONS[i.reason], "index": int(i.index),
                 "bytes": int(i.bytes), "t": int(i.t), "tau": int(i.tau), "candidates": int(i.candidates),
+                "ms_h2d": i.ms_h2d, "ms_decode": i.ms_decode, "ms_host": i.ms_host}
+
+    def _note_ingested(self) -> None:
+        st = self.blocks_ingest_stats()
+        self.tau, self.n_rows, self.n_blocks = st["tau"], st["t"], st["n_blocks"]
+
+    def ingest_blocks_cbor(self, data) -> BlockSoA:
+        """Decode a block file (blocks.cbor) from its CBOR bytes and keep the
+        step arrays in the context: on the device for a canonical file (a
+        declined one goes through the host decoder, with the same result).
+        Returns the blocks' fields and step counts without the step arrays
+        (enough for manifest_root()); upload_ingested() then uploads
+        (sezkp_ctx_ingest_blocks_cbor). `data`: see trace.cbor_bytes."""
+        p, n, keep = cbor_bytes(data)
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_ingest_blocks_cbor(self._h, p, n, C.byref(h), err, 1024), err)
+        del keep  # the call is synchronous
+        return BlockSoA._take(h, meta=True)
+
+    def upload_ingested(self) -> None:
+        """upload() of the pending ingest (sezkp_ctx_upload_ingested)."""
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_upload_ingested(self._h, err, 1024), err)
+        self._note_ingested()
+
+    def upload_blocks_cbor(self, data) -> None:
+        """ingest_blocks_cbor and upload_ingested in one call
+        (sezkp_ctx_upload_blocks_cbor)."""
+        p, n, keep = cbor_bytes(data)
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_upload_blocks_cbor(self._h, p, n, err, 1024), err)
+        del keep
+        self._note_ingested()
+
+    def decode_blocks_cbor(self, data) -> BlockSoA:
+        """The decode of upload_blocks_cbor alone, read back into a BlockSoA
+        (sezkp_ctx_decode_blocks_cbor); the context's trace image is untouched."""
+        p, n, keep = cbor_bytes(data)
+        h = C.c_void_p()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_decode_blocks_cbor(self._h, p, n, C.byref(h), err, 1024), err)
+        del keep
+        return BlockSoA._take(h)
+
+    def blocks_ingest_stats(self) -> dict:
+        """What the last ingest_blocks_cbor / upload_blocks_cbor /
+        decode_blocks_cbor call did (sezkp_ctx_blocks_ingest_stats): path
+        "device" or "host", the reason the device path declined ("none" when it
+        did not) with the block or step index that goes with it, bytes,
+        n_blocks, t, tau, the candidate counts, and the times ms_h2d, ms_decode
+        (HIP events) and ms_host."""
+        i = BlocksIngestInfo()
+        rc = lib.sezkp_ctx_blocks_ingest_stats(self._h, C.byref(i))
+        if rc != 0:
+            raise SezkpError(rc, "blocks_ingest_stats: no decode call on this context yet, or a proof is in flight")
+        return {"path": INGEST_PATHS[i.path], "reason": BLOCKS_INGEST_REASONS[i.reason], "index": int(i.index),
+                "bytes": int(i.bytes), "n_blocks": int(i.n_blocks), "t": int(i.t), "tau": int(i.tau),
+                "block_candidates": int(i.block_candidates), "step_candidates": int(i.step_candidates),
                 "ms_h2d": i.ms_h2d, "ms_decode": i.ms_decode, "ms_host": i.ms_host}
 
     def upload_trace_rows(self, input_mv, mv, has_write, wsym, b: int, t: int, row0: int) -> None:

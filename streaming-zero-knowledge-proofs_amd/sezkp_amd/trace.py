@@ -179,3 +179,13 @@ def trace_cbor_head(data):
     if not lib.sezkp_trace_cbor_head(p, n, C.byref(t), C.byref(tau), C.byref(off)):
         return None
     return t.value, tau.value, off.value
+
+
+def blocks_cbor_head(data):
+    """(n_blocks, tau, first_off) when the bytes start with the canonical head
+    of a block file the device decoder takes, else None (sezkp_blocks_cbor_head)."""
+    p, n, _keep = cbor_bytes(data)
+    nb, tau, off = C.c_uint32(), C.c_uint32(), C.c_uint64()
+    if not lib.sezkp_blocks_cbor_head(p, n, C.byref(nb), C.byref(tau), C.byref(off)):
+        return None
+    return nb.value, tau.value, off.value
