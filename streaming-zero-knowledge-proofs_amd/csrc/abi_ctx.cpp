@@ -555,7 +555,7 @@ int32_t sezkp_stark_v1_prove_trace(const sezkp_trace_view* trace, uint32_t flags
   return rc;
 }
 
-// ---- trace files decoded on the device (ctx_trace_cbor.cpp)
+// ---- trace files decoded on the device (ctx_cbor.cpp)
 int32_t sezkp_ctx_upload_trace_cbor(sezkp_ctx* ctx, const uint8_t* data, size_t len, uint32_t b, char* err,
                                     size_t err_len) {
   return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
@@ -650,7 +650,7 @@ int32_t sezkp_stark_v1_prove_trace_cbor(const uint8_t* data, size_t len, uint32_
   return rc;
 }
 
-// ---- block files decoded on the device (ctx_blocks_cbor.cpp)
+// ---- block files decoded on the device (ctx_cbor.cpp)
 // the block fields and step_start of a decoded store as a handle without steps
 static sezkp_blocks* blocks_meta_handle(const BlockStore& src) {
   std::unique_ptr<sezkp_blocks> b(new sezkp_blocks());

@@ -1,11 +1,13 @@
 // blocks_cbor_plan.h — what the host and the device agree on when a block file
 // (Vec<BlockSummary> as CBOR, sezkp-core io.rs:57-65, types.rs:116-151) is
-// decoded from its bytes on the device (blocks_cbor.hip,
-// sezkp_ctx_ingest_blocks_cbor): the canonical form, the two signatures, the
-// strict parsers of a block's head and tail, and the head check. Plain C++,
-// no HIP type: tools/blocks_cbor_check.cpp runs all of it serially under the
-// sanitizers on a machine without a GPU. The accessors, the integer heads and
-// the step parser are trace_cbor_plan.h's, unchanged.
+// decoded from its bytes on the device (cbor_decode.hip,
+// sezkp_ctx_ingest_blocks_cbor): the canonical form, the strict parsers of a
+// block's head and tail, the head check, and the body of the heads, steps and
+// chain passes. Plain C++, no HIP type: tools/cbor_check.cpp calls the same
+// passes index by index under the sanitizers on a machine without a GPU. The
+// accessors, both signatures, the mark passes, the integer heads and the step
+// parser are trace_cbor_plan.h's: a TraceFile's decoder is this one's step
+// half.
 //
 // The canonical form is what ciborium and encode_blocks_cbor write:
 //   file   array(B) head, B >= 1
@@ -20,7 +22,7 @@
 // (the host decoder casts what is outside; the device declines it, so the
 // host answers). tau <= 255 is block 0's window count.
 //
-// The decode (serially in the check tool, one kernel each on the device):
+// The decode (index by index in the check tool, one kernel each on the device):
 //   mark     every position from first_off on that starts AE 67 "version" is
 //            a block candidate, every one that starts A2 68 "input_mv" a step
 //            candidate; the first B and the first t_max in file order are stored;
@@ -44,25 +46,6 @@
 #include "trace_cbor_plan.h"
 
 namespace sezkp {
-
-constexpr uint32_t BLOCKS_CBOR_SIG_LEN = 9;
-constexpr uint64_t CBOR_BSIG_LO = 0x6F697372657667AEull;  // AE 67 'v' 'e' 'r' 's' 'i' 'o'
-constexpr uint32_t CBOR_BSIG_HI = 0x6Eu;                   // 'n'
-// bit s: the block signature starts at byte s of a (it may end in b)
-TRACE_CBOR_HD inline uint32_t cbor_block_sig_mask(const Cbor16& a, const Cbor16& b) {
-  const uint64_t w[4] = {a.lo, a.hi, b.lo, b.hi};
-  uint32_t m = 0;
-#if defined(__HIP_DEVICE_COMPILE__)
-#pragma unroll
-#endif
-  for (int s = 0; s < 16; s++) {
-    const int q = s >> 3, r = (s & 7) * 8;
-    const uint64_t x = r ? (w[q] >> r) | (w[q + 1] << (64 - r)) : w[q];
-    const uint64_t y = r ? (w[q + 1] >> r) | (w[q + 2] << (64 - r)) : w[q + 1];
-    if (x == CBOR_BSIG_LO && (uint32_t)(y & 0xFFu) == CBOR_BSIG_HI) m |= 1u << s;
-  }
-  return m;
-}
 
 // ------------------------------------------------------------ strict items
 // a text key of n <= 16 bytes (head byte included), little endian in lo | hi
@@ -325,18 +308,89 @@ struct BlocksCborVerdict {
   uint64_t bad_tail;  // block whose tail does not parse or does not end at the next block / at len
 };
 
+// Heads are good and t fits: all B heads parsed, so t is the file's step
+// count, and that many rows and candidates are there. The step and chain
+// passes run only then.
+TRACE_CBOR_HD inline bool blocks_cbor_heads_fit(const BlocksCborVerdict& v, uint64_t B, uint64_t t_max) {
+  return v.block_candidates >= B && v.bad_head == ~0ull && v.t <= t_max && v.step_candidates >= v.t;
+}
+
+// ------------------------------------------------------------ the passes
+// The body of each per-index pass, for the kernels of cbor_decode.hip and,
+// index by index, for the check tool. cand_b: B words; cand_s, ends: t_max
+// words; the arrays: t_max and t_max * tau elements; T: the tables of B
+// blocks. V starts as all ones but for the two candidate counts. `lower`: see
+// CborSerialMin.
+//
+// heads, index k: block k's head from block candidate k. With fewer than B
+// candidates nothing is parsed, but n_k is written all the same: the scan
+// reads all B of them.
+template <class Min>
+TRACE_CBOR_HD inline void blocks_cbor_head_pass(const CborSpan& s, uint64_t lo, const uint64_t* cand_b, uint64_t B,
+                                                uint32_t tau, const BlocksCborTables& T, BlocksCborVerdict* V,
+                                                uint64_t k, Min lower) {
+  if (k >= B) return;
+  if (V->block_candidates < B) {
+    T.n_steps[k] = 0;
+    T.steps_off[k] = 0;
+    return;
+  }
+  const uint64_t c = cand_b[k], o = k * tau;
+  BlockCborHead h{};
+  uint64_t end = cbor_parse_block_head(s, c, tau, false, h, T.win_left + o, T.win_right + o, T.off_in + o, T.off_out + o);
+  if (k == 0 && c != lo) end = 0;
+  blocks_cbor_store_head(T, k, h, end);
+  if (!end) lower(&V->bad_head, k);
+}
+// steps, index i: step i from step candidate i, its end, and its link: step
+// i + 1 starts where step i ends unless it is the first of a block (then the
+// chain pass checks both sides). The search through step_start runs only at a
+// mismatch: B - 1 times in a canonical file.
+template <class Min>
+TRACE_CBOR_HD inline void blocks_cbor_step_pass(const CborSpan& s, const uint64_t* cand_s, uint64_t t_max, uint64_t B,
+                                                const uint64_t* step_start, uint32_t tau, int8_t* input_mv, int8_t* mv,
+                                                uint8_t* has_write, uint16_t* wsym, uint64_t* ends,
+                                                BlocksCborVerdict* V, uint64_t i, Min lower) {
+  const uint64_t t = V->t;
+  if (!blocks_cbor_heads_fit(*V, B, t_max) || i >= t) return;
+  const uint64_t c = cand_s[i], o = i * tau;
+  const uint64_t end = cbor_parse_step(s, c, tau, input_mv + i, mv + o, has_write + o, wsym + o);
+  ends[i] = end;
+  if (!end) {
+    lower(&V->bad_step, i);
+    return;
+  }
+  if (i + 1 < t && cand_s[i + 1] != end) {
+    const uint64_t k = blocks_cbor_block_of(step_start, B, i + 1);
+    if (step_start[k] != i + 1) lower(&V->bad_link, i + 1);
+  }
+}
+// chain, index k: block k's two ends: its first step lies right behind its
+// head, and behind its last step the tail runs up to the next block candidate
+// (to len for the last block).
+template <class Min>
+TRACE_CBOR_HD inline void blocks_cbor_chain_pass(const CborSpan& s, const uint64_t* cand_b, const uint64_t* cand_s,
+                                                 uint64_t t_max, uint64_t B, uint32_t tau, const BlocksCborTables& T,
+                                                 const uint64_t* ends, BlocksCborVerdict* V, uint64_t k, Min lower) {
+  if (!blocks_cbor_heads_fit(*V, B, t_max) || k >= B) return;
+  const uint64_t a = T.step_start[k], n = T.n_steps[k];  // n >= 1, a + n <= t
+  if (cand_s[a] != T.steps_off[k]) lower(&V->bad_link, a);
+  const uint64_t e = ends[a + n - 1];
+  if (!e) return;  // the step did not parse: bad_step has it
+  const uint64_t tail_end = cbor_parse_block_tail(s, e, tau);
+  const uint64_t want = k + 1 < B ? cand_b[k + 1] : s.len;
+  if (!tail_end || tail_end != want) lower(&V->bad_tail, k);
+}
+
 // What the host makes of the verdict: SEZKP_BLOCKS_R_* by value (sezkp_stark.h)
 // and the index that goes with it. Shared with the check tool.
-struct BlocksCborDecision {
-  uint32_t reason = 0;
-  uint64_t index = 0;
-};
-inline BlocksCborDecision blocks_cbor_decide(const BlocksCborVerdict& v, const BlocksCborHead& h) {
-  BlocksCborDecision d;
-  if (v.block_candidates < h.n_blocks) d.reason = 2;
-  else if (v.bad_head != ~0ull) d.reason = 4, d.index = v.bad_head;
-  else if (v.t > h.t_max || v.step_candidates < v.t) d.reason = 3;
-  else if (v.bad_step != ~0ull && v.bad_step <= v.bad_link) d.reason = 5, d.index = v.bad_step;
+inline CborDecision blocks_cbor_decide(const BlocksCborVerdict& v, const BlocksCborHead& h) {
+  CborDecision d;
+  if (!blocks_cbor_heads_fit(v, h.n_blocks, h.t_max)) {
+    if (v.block_candidates < h.n_blocks) d.reason = 2;
+    else if (v.bad_head != ~0ull) d.reason = 4, d.index = v.bad_head;
+    else d.reason = 3;
+  } else if (v.bad_step != ~0ull && v.bad_step <= v.bad_link) d.reason = 5, d.index = v.bad_step;
   else if (v.bad_link != ~0ull) d.reason = 6, d.index = v.bad_link;
   else if (v.bad_tail != ~0ull) d.reason = 7, d.index = v.bad_tail;
   return d;

@@ -237,8 +237,7 @@ sezkp_ctx::~sezkp_ctx() {
   release_spares();
   audit.release();
   vfy.release();
-  cbor.release();
-  bcbor.release();
+  cbuf.release();
   dict.release();
   for (auto& e : ev)
     if (e) (void)hipEventDestroy(e);

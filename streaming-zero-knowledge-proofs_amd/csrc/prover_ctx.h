@@ -1,7 +1,6 @@
 // prover_ctx.h — the prover context (struct sezkp_ctx) and what its units
 // share: ctx.cpp (life of a context), ctx_upload.cpp, ctx_trace.cpp,
-// ctx_trace_cbor.cpp and ctx_blocks_cbor.cpp (trace and block files decoded
-// on the device), ctx_services.cpp
+// ctx_cbor.cpp (trace and block files decoded on the device), ctx_services.cpp
 // (audit, batch verify), proof_run.cpp (one proof) and the C ABI in
 // abi_ctx.cpp / abi_kernels.cpp. Internal to the library: nothing
 // outside csrc/ includes it.
@@ -218,54 +217,62 @@ struct VerifyBuffers {
   void release();
 };
 
-// TraceFile CBOR decoded on the device (sezkp_ctx_upload_trace_cbor,
-// ctx_trace_cbor.cpp): the file's bytes, the tile counts and their scan, the
-// candidate offsets, the decoded step arrays (wsym | mv | has_write |
-// input_mv, one block) and the verdict words; a pinned block that pageable
-// bytes are staged through, in two halves, and a pinned landing place for the
-// verdict. Like the verifier's buffers they live outside the upload
-// workspace, grow on demand and are kept.
-struct TraceCborBuffers {
+// CBOR files decoded on the device (ctx_cbor.cpp): a TraceFile
+// (sezkp_ctx_upload_trace_cbor) and a block file (sezkp_ctx_ingest_blocks_cbor).
+// One set of device blocks serves both, one ingest at a time, of either kind
+// (sezkp_ctx::cbor_claim): the file's bytes; per signature kind (0: steps,
+// 1: blocks, a block file's only) the tile counts, their scan and the
+// candidate offsets; the steps' ends and the block tables (a block file's
+// only); the decoded step arrays in one block; the verdict words and their
+// pinned landing place, sized for the larger verdict; a pinned block that
+// pageable bytes are staged through, in two halves. Like the verifier's
+// buffers they live outside the upload workspace, grow on demand and are kept.
+struct CborStepArrays {
+  uint16_t* wsym;
+  int8_t* mv;
+  uint8_t* has_write;
+  int8_t* input_mv;
+};
+struct CborBuffers {
   uint8_t* d_bytes = nullptr;
   size_t bytes_cap = 0;
-  uint32_t* d_counts = nullptr;
-  uint64_t* d_offs = nullptr;
-  size_t tiles_cap = 0;  // tiles; the other capacities in bytes
-  uint64_t* d_cand = nullptr;
-  size_t cand_cap = 0;
-  uint8_t* d_arrays = nullptr;
-  size_t arrays_cap = 0;
-  TraceCborVerdict* d_verdict = nullptr;
-  TraceCborVerdict* h_verdict = nullptr;  // pinned
-  uint8_t* h_stage = nullptr;             // pinned, 2 * STAGE_HALF bytes
-  hipEvent_t stage_ev[2]{};
-  hipEvent_t ev[3]{};  // before the copy, after it, after the kernels
-  static constexpr size_t STAGE_HALF = (size_t)8 << 20;
-  sezkp_trace_ingest_info info{};
-  bool have_info = false;
-  void release();
-};
-
-// Block-file CBOR decoded on the device (sezkp_ctx_ingest_blocks_cbor,
-// ctx_blocks_cbor.cpp). The file's bytes, the step candidates and the decoded
-// step arrays use TraceCborBuffers' blocks (one ingest at a time, of either
-// kind); here is what a block file needs besides: the second kind's tile
-// words, the block candidates, the steps' ends, the block tables and the
-// verdict. `pend`: the ingest that sezkp_ctx_upload_ingested consumes: every
-// block field and step_start on the host, the step arrays in `steps` (device
-// memory after a device decode, else pend's own vectors).
-struct BlocksCborBuffers {
-  uint32_t* d_counts = nullptr;
-  uint64_t* d_offs = nullptr;
-  size_t tiles_cap = 0;  // tiles; the other capacities in bytes
-  uint64_t* d_cand = nullptr;
-  size_t cand_cap = 0;
+  uint32_t* d_counts[2]{};
+  uint64_t* d_offs[2]{};
+  size_t tiles_cap[2]{};  // tiles; the other capacities in bytes
+  uint64_t* d_cand[2]{};
+  size_t cand_cap[2]{};
   uint64_t* d_ends = nullptr;
   size_t ends_cap = 0;
   uint8_t* d_tables = nullptr;
   size_t tables_cap = 0;
-  BlocksCborVerdict* d_verdict = nullptr;
-  BlocksCborVerdict* h_verdict = nullptr;  // pinned
+  uint8_t* d_arrays = nullptr;
+  size_t arrays_cap = 0;
+  void* d_verdict = nullptr;
+  void* h_verdict = nullptr;   // pinned
+  uint8_t* h_stage = nullptr;  // pinned, 2 * STAGE_HALF bytes
+  hipEvent_t stage_ev[2]{};
+  hipEvent_t ev[3]{};  // before the copy, after it, after the kernels
+  static constexpr size_t STAGE_HALF = (size_t)8 << 20;
+  static constexpr size_t VERDICT_BYTES = sizeof(BlocksCborVerdict);
+  static_assert(sizeof(TraceCborVerdict) <= VERDICT_BYTES, "one verdict pair for both formats");
+  // The four step arrays of `rows` steps of tau tapes, grown to fit: one block,
+  // wsym | mv | has_write | input_mv (the widest first, so each is aligned),
+  // rows * tau cells each and rows for input_mv. This is the layout every
+  // reader of a decoded file's steps goes by.
+  CborStepArrays step_arrays(uint64_t rows, uint32_t tau);
+  void tile_words(int kind, size_t ntiles);  // d_counts / d_offs of a kind, ntiles words each
+  void verdict_pair();                       // d_verdict / h_verdict, once
+  void release();
+};
+// what each format keeps to itself: the last call's stats, and for a block
+// file `pend`, the ingest that sezkp_ctx_upload_ingested consumes: every block
+// field and step_start on the host, the step arrays in `steps` (CborBuffers'
+// d_arrays after a device decode, else pend's own vectors)
+struct TraceCborIngest {
+  sezkp_trace_ingest_info info{};
+  bool have_info = false;
+};
+struct BlocksCborIngest {
   sezkp_blocks_ingest_info info{};
   bool have_info = false;
   BlockStore pend;
@@ -275,7 +282,6 @@ struct BlocksCborBuffers {
     pending = false;
     pend = BlockStore();
   }
-  void release();
 };
 // a device block of at least `bytes` bytes: kept when large enough, else
 // replaced by one a quarter larger than asked for (contents undefined)
@@ -515,21 +521,29 @@ struct sezkp_ctx {
   void verify_batch(const sezkp_proof_ref* proofs, uint32_t n, sezkp_verify_result* out);
   // full-trace AIR audit of the active trace image (bitmaps: null or (n + 7) / 8 host bytes)
   void air_audit(sezkp_air_audit* out, uint8_t* violating_bits, uint8_t* rejectable_bits);
-  TraceCborBuffers cbor;
+  CborBuffers cbuf;
+  // One ingest at a time, of either kind: before cbuf is rewritten, whatever
+  // still reads it is over: an upload on st (synchronised here), and a pending
+  // block-file ingest, whose steps lie in cbuf.d_arrays (dropped here).
+  SEZKP_LOCAL void cbor_claim();
+  // the file's bytes into cbuf.d_bytes on st, straight from pinned memory, else
+  // through the staging block; cbuf.ev[0] before the copy, cbuf.ev[1] after it
+  SEZKP_LOCAL void cbor_bytes_to_device(const uint8_t* data, size_t len);
+  // behind the kernels: cbuf.ev[2], the format's `bytes` verdict words home and
+  // st synchronised; the events' two times (the copy, the kernels)
+  SEZKP_LOCAL const void* cbor_verdict_home(size_t bytes, double& ms_h2d, double& ms_decode);
+  TraceCborIngest cbor;
   // TraceFile CBOR bytes (host memory) to step arrays: on the device when the
-  // file is canonical (tv then points into cbor.d_arrays, complete once st is
+  // file is canonical (tv then points into cbuf.d_arrays, complete once st is
   // synchronised, which this call has done), else by the host decoder into
   // `host` (tv points there; Err SEZKP_E_DECODE with its message). b = 0 in tv.
   void decode_trace_cbor(const uint8_t* data, size_t len, BlockStore& host, sezkp_trace_view& tv);
   SEZKP_LOCAL bool decode_trace_cbor_device(const uint8_t* data, size_t len, sezkp_trace_view& tv);
-  // the file's bytes into cbor.d_bytes on st, straight from pinned memory, else
-  // through the staging block; cbor.ev[0] before the copy, cbor.ev[1] after it
-  SEZKP_LOCAL void cbor_bytes_to_device(const uint8_t* data, size_t len);
-  BlocksCborBuffers bcbor;
+  BlocksCborIngest bcbor;
   // Block-file CBOR bytes (host memory) to blocks: on the device when the file
   // is canonical (the block fields and step_start come home into `out`, whose
   // step vectors stay empty; `steps` points at the step arrays in
-  // cbor.d_arrays, complete: st is synchronised), else by the host decoder
+  // cbuf.d_arrays, complete: st is synchronised), else by the host decoder
   // into `out` (`steps` points there; Err SEZKP_E_DECODE with its message).
   // Drops a pending ingest.
   void decode_blocks_cbor(const uint8_t* data, size_t len, BlockStore& out, sezkp_block_view& steps);

@@ -199,25 +199,24 @@ hipError_t launch_manifest_tree(hipStream_t st, const TraceMetaDev& M, uint64_t 
 
 // TraceFile CBOR bytes in device memory (on a 16-byte boundary) to the four
 // step-major arrays, and the verdict words the host decides on
-// (trace_cbor.hip, trace_cbor_plan.h): mark, scan, compact, parse on st.
+// (cbor_decode.hip, trace_cbor_plan.h): mark, scan, compact, parse on st.
 // counts / offs: trace_cbor_tiles(len) words; cand: t words; t >= 1.
 struct TraceCborVerdict;
 hipError_t launch_trace_cbor_decode(hipStream_t st, const uint8_t* d_bytes, uint64_t len, uint64_t steps_off, uint64_t t,
                                     uint32_t tau, uint32_t* counts, uint64_t* offs, uint64_t* cand, int8_t* input_mv,
                                     int8_t* mv, uint8_t* has_write, uint16_t* wsym, TraceCborVerdict* verdict);
-// its one-workgroup scan alone: n counts to their exclusive scan and their sum
-hipError_t launch_cbor_tile_scan(hipStream_t st, const uint32_t* counts, uint64_t n, uint64_t* offs, uint64_t* total);
 // Block-file CBOR bytes (Vec<BlockSummary>) in device memory to the block
-// tables, the four step-major arrays and the verdict words (blocks_cbor.hip,
-// blocks_cbor_plan.h). counts_* / offs_*: trace_cbor_tiles(len) words; cand_b:
-// B words; cand_s, ends: t_max words; the arrays sized by t_max.
+// tables, the four step-major arrays and the verdict words (cbor_decode.hip,
+// blocks_cbor_plan.h). By signature kind (0: steps, 1: blocks) counts / offs:
+// trace_cbor_tiles(len) words; cand[0], ends: t_max words; cand[1]: B words;
+// the arrays sized by t_max.
 struct BlocksCborTables;
 struct BlocksCborVerdict;
 hipError_t launch_blocks_cbor_decode(hipStream_t st, const uint8_t* d_bytes, uint64_t len, uint64_t first_off,
-                                     uint64_t B, uint32_t tau, uint64_t t_max, uint32_t* counts_b, uint32_t* counts_s,
-                                     uint64_t* offs_b, uint64_t* offs_s, uint64_t* cand_b, uint64_t* cand_s,
-                                     uint64_t* ends, const BlocksCborTables& T, int8_t* input_mv, int8_t* mv,
-                                     uint8_t* has_write, uint16_t* wsym, BlocksCborVerdict* verdict);
+                                     uint64_t B, uint32_t tau, uint64_t t_max, uint32_t* const counts[2],
+                                     uint64_t* const offs[2], uint64_t* const cand[2], uint64_t* ends,
+                                     const BlocksCborTables& T, int8_t* input_mv, int8_t* mv, uint8_t* has_write,
+                                     uint16_t* wsym, BlocksCborVerdict* verdict);
 
 // Per-row constraint sums of the composition (k_compose_terms): everything
 // of C(i) that does not depend on the transcript, summed over the tapes

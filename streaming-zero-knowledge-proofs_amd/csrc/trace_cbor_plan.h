@@ -1,9 +1,11 @@
 // trace_cbor_plan.h — what the host and the device agree on when a TraceFile
 // (sezkp-trace format.rs:59-68, io.rs) is decoded from its CBOR bytes on the
-// device (trace_cbor.hip, sezkp_ctx_upload_trace_cbor): the canonical form, the
-// signature that starts a step record, the strict step parser and the head
-// check. Plain C++, no HIP type: tools/trace_cbor_check.cpp runs all of it
-// serially under the sanitizers on a machine without a GPU.
+// device (cbor_decode.hip, sezkp_ctx_upload_trace_cbor): the canonical form, the
+// signatures that start a record, the strict step parser, the head check, and
+// the body of every per-index pass: a kernel is its index and one call of
+// cbor_lane_marks / cbor_store_marks / trace_cbor_step_pass. Plain C++, no HIP
+// type: tools/cbor_check.cpp calls the same passes index by index under the
+// sanitizers on a machine without a GPU.
 //
 // The canonical form is what ciborium and sezkp_trace_encode_cbor write:
 //   head  A4 | 67 "version" | uint | 63 "tau" | uint <= 255 | 65 "steps" | array(t)
@@ -16,8 +18,8 @@
 // exactly this form and declines everything else; a declined file goes to the
 // host pull parser (codec.cpp), which alone reports errors.
 //
-// The decode, in four passes (serially in the check tool, one kernel each on
-// the device):
+// The decode, in four passes (index by index in the check tool, one kernel
+// each on the device):
 //   mark     every byte position from steps_off on that starts the 10-byte
 //            signature A2 68 "input_mv" is a candidate;
 //   compact  the candidates in file order, the first t stored, all counted;
@@ -93,10 +95,23 @@ TRACE_CBOR_HD inline Cbor16 cbor_load16(const CborSpan& s, uint64_t pos) {
 }
 
 // ------------------------------------------------------------ mark
+// The signatures by kind: 0 starts a step record (A2 68 "input_mv"), 1 a block
+// of a block file (AE 67 "version", blocks_cbor_plan.h). The first 8 bytes in
+// lo, the rest in hi under hi_mask. A signature's first byte occurs nowhere
+// else in it, so two candidates of one kind lie at least len positions apart.
 constexpr uint64_t CBOR_SIG_LO = 0x5F7475706E6968A2ull;  // A2 68 'i' 'n' 'p' 'u' 't' '_'
 constexpr uint32_t CBOR_SIG_HI = 0x766Du;                // 'm' 'v'
-// bit s: the signature starts at byte s of a (it may end in b, the 16 bytes after a)
+constexpr uint32_t BLOCKS_CBOR_SIG_LEN = 9;
+struct CborSig {
+  uint64_t lo;
+  uint32_t hi, hi_mask;
+};
+constexpr CborSig CBOR_SIGS[2] = {{CBOR_SIG_LO, CBOR_SIG_HI, 0xFFFFu},
+                                  {0x6F697372657667AEull, 0x6Eu, 0xFFu}};  // AE 67 'v' 'e' 'r' 's' 'i' 'o' | 'n'
+// bit s: the signature of KIND starts at byte s of a (it may end in b, the 16 bytes after a)
+template <int KIND>
 TRACE_CBOR_HD inline uint32_t cbor_sig_mask(const Cbor16& a, const Cbor16& b) {
+  constexpr CborSig S = CBOR_SIGS[KIND];
   const uint64_t w[4] = {a.lo, a.hi, b.lo, b.hi};
   uint32_t m = 0;
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -106,9 +121,35 @@ TRACE_CBOR_HD inline uint32_t cbor_sig_mask(const Cbor16& a, const Cbor16& b) {
     const int q = s >> 3, r = (s & 7) * 8;
     const uint64_t x = r ? (w[q] >> r) | (w[q + 1] << (64 - r)) : w[q];
     const uint64_t y = r ? (w[q + 1] >> r) | (w[q + 2] << (64 - r)) : w[q + 1];
-    if (x == CBOR_SIG_LO && (uint32_t)(y & 0xFFFFu) == CBOR_SIG_HI) m |= 1u << s;
+    if (x == S.lo && (uint32_t)(y & S.hi_mask) == S.hi) m |= 1u << s;
   }
   return m;
+}
+// One lane of the mark passes: the candidates of the first KINDS kinds among
+// the 16 positions from pos (bit s of m[kind]: pos + s), none before lo. At
+// most two of a kind (both signatures are 9 bytes or longer).
+static_assert(BLOCKS_CBOR_SIG_LEN >= 9 && TRACE_CBOR_SIG_LEN >= 9, "at most two candidates of a kind in 16 positions");
+template <int KINDS>
+TRACE_CBOR_HD inline void cbor_lane_marks(const CborSpan& s, uint64_t lo, uint64_t pos, uint32_t (&m)[KINDS]) {
+  for (int q = 0; q < KINDS; q++) m[q] = 0u;
+  if (pos >= s.len) return;
+  const Cbor16 a = cbor_load16(s, pos), b = cbor_load16(s, pos + 16);
+  m[0] = cbor_sig_mask<0>(a, b);
+  if constexpr (KINDS > 1) m[1] = cbor_sig_mask<1>(a, b);
+  if (pos < lo) {
+    const uint32_t keep = lo - pos >= 16 ? 0u : (0xFFFFu << (uint32_t)(lo - pos)) & 0xFFFFu;
+    for (int q = 0; q < KINDS; q++) m[q] &= keep;
+  }
+}
+// One lane of the compact pass: its marks of one kind are candidates idx,
+// idx + 1, ... in file order; those below cap are stored. The index behind them.
+TRACE_CBOR_HD inline uint64_t cbor_store_marks(uint32_t m, uint64_t pos, uint64_t idx, uint64_t* cand, uint64_t cap) {
+  while (m) {
+    if (idx < cap) cand[idx] = pos + (uint32_t)__builtin_ctz(m);
+    m &= m - 1u;
+    idx++;
+  }
+  return idx;
 }
 
 // ------------------------------------------------------------ strict items
@@ -253,5 +294,53 @@ struct TraceCborVerdict {
   uint64_t bad_link;
   uint64_t tail_off;
 };
+// How a failing index is lowered into a verdict word is all that differs
+// between the device and a serial run: an atomic minimum there (cbor_decode.hip),
+// this one here.
+struct CborSerialMin {
+  void operator()(uint64_t* word, uint64_t i) const {
+    if (i < *word) *word = i;
+  }
+};
+
+// ------------------------------------------------------------ the step pass
+// Index i of the parse pass: step i from candidate i into row i of the arrays
+// (t and t * tau elements), and its link: step 0 starts at lo, step i + 1
+// where step i ends. With fewer than t candidates nothing is parsed. V starts
+// as all ones but for candidates.
+template <class Min>
+TRACE_CBOR_HD inline void trace_cbor_step_pass(const CborSpan& s, uint64_t lo, const uint64_t* cand, uint64_t t,
+                                               uint32_t tau, int8_t* input_mv, int8_t* mv, uint8_t* has_write,
+                                               uint16_t* wsym, TraceCborVerdict* V, uint64_t i, Min lower) {
+  if (i >= t || V->candidates < t) return;
+  const uint64_t c = cand[i], o = i * tau;
+  const uint64_t end = cbor_parse_step(s, c, tau, input_mv + i, mv + o, has_write + o, wsym + o);
+  if (!end) {
+    lower(&V->bad_step, i);
+    return;
+  }
+  if (i == 0 && c != lo) lower(&V->bad_link, 0);
+  if (i + 1 < t) {
+    if (cand[i + 1] != end) lower(&V->bad_link, i + 1);
+  } else {
+    V->tail_off = end;
+  }
+}
+
+// What the host makes of the verdict: SEZKP_INGEST_R_* by value (sezkp_stark.h)
+// and the index that goes with it; 0: the steps are taken, the tail at
+// v.tail_off is the caller's to check (codec.cpp's trace_cbor_tail_ok). A file
+// of no steps has the verdict {0, ~0, ~0, steps_off}. Shared with the check tool.
+struct CborDecision {
+  uint32_t reason = 0;
+  uint64_t index = 0;
+};
+inline CborDecision trace_cbor_decide(const TraceCborVerdict& v, const TraceCborHead& h) {
+  CborDecision d;
+  if (v.candidates < h.t) d.reason = 2;
+  else if (v.bad_step != ~0ull && v.bad_step <= v.bad_link) d.reason = 3, d.index = v.bad_step;
+  else if (v.bad_link != ~0ull) d.reason = 4, d.index = v.bad_link;
+  return d;
+}
 
 }  // namespace sezkp

@@ -6,14 +6,14 @@
   without a device;
 * sezkp_blocks_cbor_head on both reference fixtures and on heads that leave
   the canonical form;
-* csrc/blocks_cbor_plan.h through the stand-alone tools/blocks_cbor_check.cpp,
-  built with the address and undefined-behaviour sanitizers (nothing is loaded
-  into Python): the device decoder's mark, compact, heads, steps and chain
-  passes run serially over corpora A, B and C (tests/blocks_cbor_corpus.py)
-  and over every prefix of a small file. The tool never takes a file the host
-  decoder refuses, decodes what it takes as the host decoder does, takes every
-  file of A, and the sanitizers stay silent: this is the out-of-bounds check of
-  the accessor every lane reads through."""
+* csrc/blocks_cbor_plan.h through the stand-alone tools/cbor_check.cpp (mode
+  `blocks`), built with the address and undefined-behaviour sanitizers (nothing
+  is loaded into Python): the device decoder's own mark, compact, heads, steps
+  and chain passes, index by index, over corpora A, B and C
+  (tests/blocks_cbor_corpus.py) and over every prefix of a small file. The tool
+  never takes a file the host decoder refuses, decodes what it takes as the
+  host decoder does, takes every file of A, and the sanitizers stay silent:
+  this is the out-of-bounds check of every read and write a lane makes."""
 import ctypes as C
 import json
 import os
@@ -127,17 +127,18 @@ def test_blocks_cbor_head(product):
 # ------------------------------------------------------------ the check tool
 @pytest.fixture(scope="module")
 def check_tool(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("blocks_cbor_check") / "blocks_cbor_check")
+    exe = str(tmp_path_factory.mktemp("cbor_check") / "cbor_check")
+    csrc = os.path.join(PKG, "csrc")
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tools", "blocks_cbor_check.cpp")],
-                   check=True)
+                    "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tools", "cbor_check.cpp"),
+                    os.path.join(csrc, "codec.cpp"), os.path.join(csrc, "host_crypto.cpp"), "-pthread"], check=True)
     return exe
 
 
 def run_tool(exe, files):
     """One verdict per file: ("decline", reason) or ("device", {array: (count, crc32)})."""
     feed = b"".join(struct.pack("<Q", len(f)) + f for f in files)
-    r = subprocess.run([exe, "batch"], input=feed, capture_output=True)
+    r = subprocess.run([exe, "blocks", "batch"], input=feed, capture_output=True)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     assert r.stderr == b"", r.stderr[-2000:]  # a sanitizer report
     lines = r.stdout.decode().splitlines()
@@ -177,7 +178,7 @@ def check_against_host(product, name, verdict, raw, must_take=False, pin=None):
 
 
 def test_tool_reports_the_bounds(check_tool):
-    r = subprocess.run([check_tool, "tiling"], capture_output=True, text=True, check=True)
+    r = subprocess.run([check_tool, "blocks", "tiling"], capture_output=True, text=True, check=True)
     tl = json.loads(r.stdout)
     assert tl["tile"] == K.tiling()["tile"] and (tl["block_sig_len"], tl["step_sig_len"]) == (9, 10)
     # the shortest canonical block of each tau is exactly the bound B is checked against

@@ -5,14 +5,15 @@
   SEZKP_E_DECODE with its message, all without a device;
 * sezkp_trace_cbor_head on the fixture and on heads that leave the canonical
   form;
-* csrc/trace_cbor_plan.h through the stand-alone tools/trace_cbor_check.cpp,
-  built with the address and undefined-behaviour sanitizers (nothing is loaded
-  into Python): the device decoder's mark, compact, parse and chain passes run
-  serially over corpora A, B and C (tests/trace_cbor_corpus.py) and over every
-  prefix of a small file. The tool never takes a file the host decoder
-  refuses, decodes what it takes as the host decoder does, takes every file
-  of A, and the sanitizers stay silent: this is the out-of-bounds check of the
-  accessor every lane reads through."""
+* csrc/trace_cbor_plan.h through the stand-alone tools/cbor_check.cpp (mode
+  `trace`), built with the address and undefined-behaviour sanitizers (nothing
+  is loaded into Python): the device decoder's own mark, compact and parse
+  passes, index by index, over corpora A, B and C (tests/trace_cbor_corpus.py)
+  and over every prefix of a small file. The tool never takes a file the host
+  decoder refuses, decodes what it takes as the host decoder does, takes every
+  file of A, declines the pinned files of B for the reason the product gives
+  (they share trace_cbor_decide), and the sanitizers stay silent: this is the
+  out-of-bounds check of every read and write a lane makes."""
 import ctypes as C
 import os
 import struct
@@ -111,10 +112,10 @@ def test_trace_cbor_head(product):
 # ------------------------------------------------------------ the check tool
 @pytest.fixture(scope="module")
 def check_tool(tmp_path_factory):
-    exe = str(tmp_path_factory.mktemp("trace_cbor_check") / "trace_cbor_check")
+    exe = str(tmp_path_factory.mktemp("cbor_check") / "cbor_check")
     csrc = os.path.join(PKG, "csrc")
     subprocess.run(["g++", "-std=c++17", "-g", "-O1", "-Wall", "-Werror", "-fsanitize=address,undefined",
-                    "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tools", "trace_cbor_check.cpp"),
+                    "-fno-sanitize-recover=all", "-o", exe, os.path.join(ROOT, "tools", "cbor_check.cpp"),
                     os.path.join(csrc, "codec.cpp"), os.path.join(csrc, "host_crypto.cpp"), "-pthread"], check=True)
     return exe
 
@@ -122,7 +123,7 @@ def check_tool(tmp_path_factory):
 def run_tool(exe, files):
     """One verdict per file: ("decline", reason) or ("device", arrays)."""
     feed = b"".join(struct.pack("<Q", len(f)) + f for f in files)
-    r = subprocess.run([exe, "batch"], input=feed, capture_output=True)
+    r = subprocess.run([exe, "trace", "batch"], input=feed, capture_output=True)
     assert r.returncode == 0, (r.returncode, r.stderr[-2000:])
     assert r.stderr == b"", r.stderr[-2000:]  # a sanitizer report
     lines = r.stdout.decode().splitlines()
@@ -163,7 +164,7 @@ def check_against_host(product, name, verdict, raw, must_take=False, must_declin
 
 def test_tool_reports_the_tiling(check_tool):
     import json
-    r = subprocess.run([check_tool, "tiling"], capture_output=True, text=True, check=True)
+    r = subprocess.run([check_tool, "trace", "tiling"], capture_output=True, text=True, check=True)
     tl = json.loads(r.stdout)
     assert {k: tl[k] for k in K.tiling()} == K.tiling()
     assert (tl["step_min"], tl["step_max"]) == ([18, 114, 307], [19, 139, 380])  # 17 + h + 12 tau, 18 + h + 15 tau
@@ -181,9 +182,19 @@ def test_corpus_a_is_taken_and_decoded_as_the_host_does(product, check_tool):
 
 def test_corpus_b_is_declined_or_decoded_alike(product, check_tool):
     files = K.corpus_b()
-    for (name, raw, pinned), v in zip(files, run_tool(check_tool, [f for _, f, _ in files])):
+    verdicts = run_tool(check_tool, [f for _, f, _ in files])
+    for (name, raw, pinned), v in zip(files, verdicts):
         assert K.host_decode(product, raw)[0] == "ok", name  # B: files the host decoder accepts
         check_against_host(product, name, v, raw, must_decline=pinned)
+    # the reasons tests/test_gpu_trace_cbor.py pins on the device: the tool decides through
+    # trace_cbor_decide, as the product does
+    got = {name: v for (name, _, _), v in zip(files, verdicts)}
+    assert got["non_minimal_int"] == ("decline", "step 7")
+    assert got["unknown_tape_key"] == ("decline", "step 9")
+    assert got["indefinite_steps"] == got["top_level_key_order"] == ("decline", "head")
+    assert got["meta_map"] == ("decline", "tail")
+    assert got["tapes_before_input_mv"][0] == "decline"
+    assert got["tapes_before_input_mv"][1].split()[0] in ("candidates", "step", "chain")
 
 
 def test_corpus_c_is_never_taken(product, check_tool):
