@@ -1,7 +1,7 @@
 // compose.h — the AIR composition value C(i) (air.rs:49-136, prover.rs:142-158)
 // from the per-row constraint sums of k_compose_terms (air_rows.hip), once the
 // transcript has the alphas and the mask. Shared by k_compose_combine
-// (air_rows.hip) and k_inv_base (ntt.hip, fused with the DEEP quotient).
+// (air_rows.hip) and k_inv_base (deep_base.hip, fused with the DEEP quotient).
 #pragma once
 #include "dev_common.h"
 #include "sezkp_internal.h"

@@ -1,5 +1,5 @@
 // gl_pow2.h — Goldilocks products by powers of two and the register
-// butterflies built on them (the four-step register passes of ntt.hip).
+// butterflies built on them (the four-step register passes of ntt_pass.hip).
 // 2 has order 192 mod p, so every root of unity w_{2^k} with k <= 6 is a power
 // of two and x * w^j is limb placement plus one or two add/sub fix-ups.
 #pragma once

@@ -53,12 +53,12 @@ struct NttPassArgs {
   uint64_t out_scale;
   // nat_tr: the last (narrow, m <= 8) DIF pass gathers the 16 blocks whose
   // outputs share 128-B lines and stores them transposed into natural order
-  // (ntt.hip gather_to_lds / lds_to_transposed)
+  // (ntt_pass.hip gather_to_lds / lds_to_transposed)
   int nat_tr;
   // k_ntt4, twiddles as loads (both off with SEZKP_NTT_TW_TABLE=0): tw_tab:
   // W[] from tw.hi alone instead of tw_pow; tw_pass: the pass twiddles
   // w_{2^(m + sL)}^(low j) at [(j << sL) + low] for a wide pass with
-  // m + sL <= K - S (ntt.hip pass_twiddles), null = the multiplication chain
+  // m + sL <= K - S (ntt_pass.hip pass_twiddles), null = the multiplication chain
   int tw_tab;
   const uint64_t* tw_pass;
 };
@@ -99,6 +99,8 @@ hipError_t launch_inv_base(hipStream_t st, const ComposeTerms& Tm, uint64_t* D, 
 hipError_t launch_q_tables(hipStream_t st, const uint64_t* partial, int logn, int logN, const DevChal* ch,
                            uint64_t* rlo, uint64_t* rhi, uint64_t* rhk, uint64_t per);
 
+// The transforms (ntt_run.cpp): each makes its request, plans it (ntt_plan.h)
+// and walks the plan; a request no kernel takes fails before any launch.
 hipError_t ntt_dif(hipStream_t st, uint64_t* a, int logN, bool inverse, const NttTables& T);
 // natural order in and out through `scratch` (n words): the first pass reads a
 // and writes scratch, the last scatters scratch back to a in natural order
@@ -111,10 +113,18 @@ hipError_t ntt_dit(hipStream_t st, uint64_t* a, int logN, bool inverse, const Nt
                    const uint64_t* src, int log_src, uint64_t inv_n, uint64_t coset_e = 0,
                    const DeepFuse* deep = nullptr, bool* fused = nullptr, const DeepPoly* dpoly = nullptr,
                    int src_logP = 0);
+// one planned pass (ntt_plan.h) to its kernel: the 256-lane forms
+// (ntt_pass.hip) and the 512-lane ones (ntt_pass512.hip); false = not a form
+// of that unit, nothing launched. pass_twiddles: the pass-twiddle table of a
+// wide k_ntt4 pass, built on first use, or null (the chain).
+struct NttPass;
+bool launch_pass256(hipStream_t st, const NttPass& p, bool dif, bool inverse, const NttPassArgs& P);
+bool launch_pass512(hipStream_t st, const NttPass& p, bool inverse, const NttPassArgs& P);
+const uint64_t* pass_twiddles(hipStream_t st, const NttTables& T, int sL, int m, bool inverse);
 hipError_t bitrev_permute(hipStream_t st, const uint64_t* in, uint64_t* out, int logN, uint64_t scale,
                           bool do_scale);
 hipError_t bitrev_inplace(hipStream_t st, uint64_t* a, int logN, uint64_t scale, bool do_scale);  // logN >= 8
-// distributed four-step NTT pieces (ntt.hip)
+// distributed four-step NTT pieces (ntt_permute.hip)
 hipError_t dntt_permute_twiddle(hipStream_t st, const uint64_t* in, uint64_t* out, int logM, const NttTables& T,
                                 uint64_t e_step, bool inverse, bool tw_src, uint64_t scale);
 hipError_t dntt_dft(hipStream_t st, uint64_t* r, int P, uint64_t Q, bool inverse);

@@ -1,4 +1,5 @@
-"""GPU parity of k_ntt4's table twiddles (SEZKP_NTT_TW_TABLE, ntt.hip).
+"""GPU parity of k_ntt4's table twiddles (SEZKP_NTT_TW_TABLE, ntt_pass.hip;
+the switch is read by the runner in ntt_run.cpp).
 
 A wide pass (sL >= 4) of m stages whose m + sL <= 16 takes its pass twiddle
 w_{2^(m + sL)}^(low j) as one load per element from a table of the pass's
@@ -8,7 +9,7 @@ tw_pow and the multiplication chain, and every k_ntt4 pass fills its W[] from
 the chains. Both arms must give the oracle's values, bit for bit.
 
 The smallest sizes with such a pass on the register kernel (m in 6..8, 16
-columns), from plan_passes / plan_passes_x16 (2^10..2^12 are one X16 tile, no
+columns), from plan_passes / plan_passes_x16 (ntt_plan.h; 2^10..2^12 are one X16 tile, no
 wide pass; below 2^10 the passes have m < 6 and run k_ntt_pass):
 
   DIF, forward and inverse (sezkp_gl_ntt without scratch: ntt_dif + bit
