@@ -267,6 +267,17 @@ int32_t sezkp_ctx_head_wide_stats(const sezkp_ctx* ctx, sezkp_head_wide_info* ou
 int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* ctx, uint32_t* cols_by_value, uint32_t* cols_by_block,
                                  uint64_t* units_built);
 
+/* The first pass of the coset LDE evaluates the DEEP polynomial. Where that
+ * pass is the plain narrow register pass and the rank evaluates 2^b times as
+ * many points as the trace has rows (b = 1..3), it forms the result of its
+ * first b butterfly stages in closed form instead of loading point by point
+ * (SEZKP_DP_CLOSED=0, read per prove: always point by point); the proof bytes
+ * never depend on it. This reports the last completed prove: b, or 0 for the
+ * point-by-point load and for the per-point DEEP division (0 before the first
+ * prove of an upload). Returns SEZKP_OK, or SEZKP_E_INVALID for a null
+ * argument or while a proof is in flight. */
+int32_t sezkp_ctx_lde_closed_stages(const sezkp_ctx* ctx, int32_t* stages);
+
 /* ------------------------------------------------ proving from a raw trace
  * Every entry point above starts from BlockSummary data: the caller has run
  * partition_trace and hashed the manifest on the host. These start from the

@@ -371,6 +371,12 @@ int32_t sezkp_ctx_pw_table_stats(const sezkp_ctx* cctx, uint32_t* cols_by_value,
   *units_built = have ? ctx->pwstat_units : 0;
   return SEZKP_OK;
 }
+int32_t sezkp_ctx_lde_closed_stages(const sezkp_ctx* cctx, int32_t* stages) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || !stages || ctx->busy()) return SEZKP_E_INVALID;  // rewritten by the proof in flight
+  *stages = ctx->loaded && ctx->have_plans ? ctx->ldestat_closed : 0;
+  return SEZKP_OK;
+}
 int32_t sezkp_ctx_comm_stats(const sezkp_ctx* ctx, sezkp_comm_stat* out, int32_t max) {
   if (!ctx || !out || max <= 0) return 0;
   int32_t cnt = 0;

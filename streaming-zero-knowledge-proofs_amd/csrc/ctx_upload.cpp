@@ -341,6 +341,8 @@ void sezkp_ctx::upload_fri_workspace(const FriPlan& fp) {
     d_dq_rlo = dalloc<uint64_t>(4096);
     d_dq_rhi = dalloc<uint64_t>(Ml > 4096 ? Ml >> 12 : 1);
     d_dq_rhk = dalloc<uint64_t>(n > 4096 ? n >> 12 : 1);
+    d_dq_rhu = dalloc<uint64_t>(n > 4096 ? n >> 12 : 1);
+    d_dq_gk = dalloc<uint64_t>(8);
   }
   d_lde = dalloc<uint64_t>(fp.lde_vals);
   if (sharded()) {

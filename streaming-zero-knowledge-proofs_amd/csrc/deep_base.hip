@@ -139,11 +139,13 @@ hipError_t launch_scale_pow_bitrev(hipStream_t st, uint64_t* a, int logn, uint64
 
 // Every WG reduces the partials (S; f(z) = K1 S, c' = f(z) K2, kappa = K3 S),
 // then grid-strides over the tables: rlo[t] = r^t, rhi[t] = c' r^(4096 t),
-// rhk[t] = kappa r^(4096 t).
+// rhk[t] = kappa r^(4096 t); or, for the closed-form first LDE stages
+// (gk != null): rlo, rhu[t] = r^(4096 t) and gk[s] = c' G[s] - kappa.
 __global__ void __launch_bounds__(NTT_THREADS) k_q_tables(const uint64_t* __restrict__ partial, uint32_t nparts,
                                                           const DevChal* __restrict__ ch, uint64_t* __restrict__ rlo,
                                                           uint64_t* __restrict__ rhi, uint32_t nhi,
-                                                          uint64_t* __restrict__ rhk, uint32_t nhk) {
+                                                          uint64_t* __restrict__ rhk, uint32_t nhk,
+                                                          uint64_t* __restrict__ rhu, uint64_t* __restrict__ gk) {
   const uint64_t K1 = ch->K1, K2 = ch->K2, K3 = ch->K3, r = ch->rho, r4096 = ch->rho4096;
   __shared__ uint64_t wsum[NTT_THREADS / 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -159,6 +161,11 @@ __global__ void __launch_bounds__(NTT_THREADS) k_q_tables(const uint64_t* __rest
   const uint64_t fz = gl_mul(K1, S), cp = gl_mul(fz, K2), kappa = gl_mul(K3, S);
   const uint64_t g0 = (uint64_t)blockIdx.x * NTT_THREADS + tid, gs = (uint64_t)gridDim.x * NTT_THREADS;
   for (uint64_t t = g0; t < 4096; t += gs) rlo[t] = gl_pow_dev(r, t);
+  if (gk) {
+    for (uint64_t t = g0; t < nhk; t += gs) rhu[t] = gl_pow_dev(r4096, t);
+    if (g0 < 8) gk[g0] = gl_sub(gl_mul(cp, ch->G[g0]), kappa);
+    return;
+  }
   for (uint64_t t = g0; t < nhi; t += gs) rhi[t] = gl_mul(cp, gl_pow_dev(r4096, t));
   for (uint64_t t = g0; t < nhk; t += gs) rhk[t] = gl_mul(kappa, gl_pow_dev(r4096, t));
 }
@@ -186,15 +193,17 @@ hipError_t launch_inv_base(hipStream_t st, const ComposeTerms& Tm, uint64_t* D, 
 }
 
 hipError_t launch_q_tables(hipStream_t st, const uint64_t* partial, int logn, int logN, const DevChal* ch,
-                           uint64_t* rlo, uint64_t* rhi, uint64_t* rhk, uint64_t per) {
-  if (logn < 4 || logN < logn || logN > 32 || !per) return hipErrorInvalidValue;
+                           uint64_t* rlo, uint64_t* rhi, uint64_t* rhk, uint64_t* rhu, uint64_t* gk, bool closed,
+                           uint64_t per) {
+  if (logn < 4 || logN < logn || logN > 32 || !per || (closed && (!rhu || !gk))) return hipErrorInvalidValue;
   const uint64_t n = 1ULL << logn;
   const uint32_t nparts = (uint32_t)((n + per - 1) / per);
   const uint32_t nhi = logN > 12 ? (1u << (logN - 12)) : 1u;
   const uint32_t nhk = logn > 12 ? (1u << (logn - 12)) : 1u;
-  const uint64_t work = std::max<uint64_t>(4096, nhi);
+  const uint64_t work = std::max<uint64_t>(4096, closed ? nhk : nhi);
   const unsigned grid = (unsigned)std::min<uint64_t>(1024, (work + NTT_THREADS - 1) / NTT_THREADS);
-  hipLaunchKernelGGL(k_q_tables, dim3(grid), dim3(NTT_THREADS), 0, st, partial, nparts, ch, rlo, rhi, nhi, rhk, nhk);
+  hipLaunchKernelGGL(k_q_tables, dim3(grid), dim3(NTT_THREADS), 0, st, partial, nparts, ch, rlo, rhi, nhi, rhk, nhk,
+                     closed ? rhu : nullptr, closed ? gk : nullptr);
   return hipGetLastError();
 }
 }  // namespace sezkp

@@ -61,6 +61,29 @@ __device__ __forceinline__ uint64_t dp_load(const NttPassArgs& P, const NttTable
   }
   return v;
 }
+// The same coefficients after the first B DIT stages, in closed form
+// (DeepPoly): the F1 points from p0 (a multiple of F1) are F1 >> B groups;
+// group g = p >> B holds qv_g + r^e0 gk[s] in slot s, e0 = bitrev(g). One
+// bit reversal, one r^e0 and one qv per group; one product and one sum per
+// point. The caller goes on with fft_dit_regs<M1, INV, B>.
+template <int F1, int B>
+__device__ __forceinline__ void dp_load_closed(const NttPassArgs& P, const NttTables& T, uint64_t p0,
+                                               uint64_t (&x)[F1]) {
+  static_assert((1 << B) <= F1 && B >= 1 && B <= 3, "a group lies inside one thread's points");
+  uint64_t gk[1 << B];
+#pragma unroll
+  for (int s = 0; s < (1 << B); s++) gk[s] = P.dp_gk[s];
+#pragma unroll
+  for (int r = 0; r < F1; r += (1 << B)) {
+    const uint64_t k = (p0 + r) >> B;
+    const uint32_t e0 = P.log_src ? (__brev((uint32_t)k) >> (32 - P.log_src)) : 0;
+    uint64_t qv = gl_mul(gl_mul(P.src[src_slot(P, k, e0)], P.inv_n), pow3(T, e0));
+    if (P.coset_e) qv = gl_mul(qv, tw_pow(T, ((uint64_t)e0 * P.coset_e) & ((1ULL << T.K) - 1), false));  // (w_N^g)^e
+    const uint64_t re = gl_mul(P.dp_rhu[e0 >> 12], P.dp_rlo[e0 & 4095]);
+#pragma unroll
+    for (int s = 0; s < (1 << B); s++) x[r + s] = gl_add(qv, gl_mul(re, gk[s]));
+  }
+}
 
 template <bool DIF>
 __global__ void __launch_bounds__(NTT_THREADS) k_ntt_pass(NttPassArgs P) {
@@ -419,11 +442,29 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt4(NttPassArgs P) {
     if (g < F2) {  // step 1: thread (c, u), registers r
       const int u = g;
       uint64_t low = 0;
+      bool closed = false;  // the load came with its first b stages done (dp_load_closed)
       if (P.dp_rlo) {  // DEEP-quotient LDE load (first pass, sL = 0, low = 0, SKIP = 0)
         const uint64_t p0 = tile_pos(G, F1 * u, c, low);
         const int b = P.dp_logN - P.log_src;
+        if constexpr (NARROW && SKIP == 0 && !X16 && !INV) {
+          if (P.dp_gk) {  // b in 1..3 (ntt_pass_dp_closed): a kernel argument, so wave-uniform
+            closed = true;
+            if (b == 3) {
+              dp_load_closed<F1, 3>(P, T, p0, x);
+              fft_dit_regs<M1, INV, 3>(x);
+            } else if (b == 2) {
+              dp_load_closed<F1, 2>(P, T, p0, x);
+              fft_dit_regs<M1, INV, 2>(x);
+            } else {
+              dp_load_closed<F1, 1>(P, T, p0, x);
+              fft_dit_regs<M1, INV, 1>(x);
+            }
+          }
+        }
+        if (!closed) {
 #pragma unroll
-        for (int r = 0; r < F1; r++) x[r] = dp_load(P, T, p0 + r, b);
+          for (int r = 0; r < F1; r++) x[r] = dp_load(P, T, p0 + r, b);
+        }
       } else if (P.src) {  // LDE replicated load (first pass, sL = 0, low = 0)
         const uint64_t p0 = tile_pos(G, F1 * u, c, low);
 #pragma unroll
@@ -469,7 +510,7 @@ __global__ void __launch_bounds__(NTT_THREADS, 4) k_ntt4(NttPassArgs P) {
           }
         }
       }
-      fft_dit_regs<M1, INV, SKIP>(x);
+      if (!closed) fft_dit_regs<M1, INV, SKIP>(x);
     }
     if (staged_load) __syncthreads();  // every thread has read its points from the image
     if (g < F2) {

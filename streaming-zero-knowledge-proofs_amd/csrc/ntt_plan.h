@@ -120,6 +120,15 @@ inline bool ntt_plan_ntt4(NttPass& p, bool dif, int K, int S) {
   return true;
 }
 
+// Whether a DEEP-polynomial first pass forms its groups in closed form
+// (DeepPoly, sezkp_internal.h) instead of loading point by point: the plain
+// narrow k_ntt4 pass of a forward LDE with b = logN - log_src in 1..3. The
+// plan is the same either way (SKIP = 0); b selects the code inside the kernel.
+inline bool ntt_pass_dp_closed(const NttPass& p, int logN, int log_src, bool inverse) {
+  const int b = logN - log_src;
+  return p.loads_dpoly && p.form == NTT4_NARROW && p.SKIP == 0 && !inverse && b >= 1 && b <= 3 && b <= p.M1;
+}
+
 // a 512-lane form: none of k_ntt4's template arguments, no pass table
 inline void ntt_plan_512(NttPass& p, NttForm form) {
   p.form = form;

@@ -39,7 +39,13 @@ static hipError_t ntt_run(hipStream_t st, const NttPlan& pl, const NttRequest& r
     P.inverse = rq.inverse ? 1 : 0;
     P.log_src = io.log_src; P.inv_n = io.inv_n;
     if (p.loads_src) { P.src = io.src; P.coset_e = io.coset_e; P.src_logP = io.src_logP; }
-    if (p.loads_dpoly) { P.dp_rlo = io.dpoly->rlo; P.dp_rhi = io.dpoly->rhi; P.dp_rhk = io.dpoly->rhk; P.dp_logN = rq.logN; }
+    if (p.loads_dpoly) {
+      P.dp_rlo = io.dpoly->rlo; P.dp_rhi = io.dpoly->rhi; P.dp_rhk = io.dpoly->rhk; P.dp_logN = rq.logN;
+      // the tables hold one form or the other (k_q_tables): a pass that cannot take them is refused
+      const bool can = ntt_pass_dp_closed(p, rq.logN, io.log_src, rq.inverse);
+      if (io.dpoly->closed && !can) return hipErrorInvalidValue;
+      if (io.dpoly->closed) { P.dp_gk = io.dpoly->gk; P.dp_rhu = io.dpoly->rhu; }
+    }
     P.nat_out = p.nat_out; P.nat_tr = p.nat_tr;
     if (p.nat_out || p.nat_tr) P.nat_logN = rq.logN;
     if (p.out_scale) P.out_scale = io.scale;
@@ -91,6 +97,14 @@ hipError_t ntt_dit(hipStream_t st, uint64_t* a, int logN, bool inverse, const Nt
   const hipError_t e = ntt_run(st, pl, rq, T, io);
   if (fused) *fused = pl.deep_fused;
   return e;
+}
+
+bool ntt_lde_dpoly_closed(int logN, int log_src, const NttTables& T) {
+  NttRequest rq{};
+  rq.logN = logN; rq.K = T.K; rq.S = T.S;
+  rq.has_src = true; rq.log_src = log_src; rq.has_dpoly = true;
+  NttPlan pl;
+  return ntt_plan(rq, pl) == NTT_PLAN_OK && pl.np > 0 && ntt_pass_dp_closed(pl.pass[0], logN, log_src, false);
 }
 
 bool ntt_dif_natural(hipStream_t st, uint64_t* a, uint64_t* scratch, int logN, bool inverse, const NttTables& T,

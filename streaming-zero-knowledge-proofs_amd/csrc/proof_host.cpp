@@ -57,6 +57,22 @@ DeepConsts deep_constants(uint64_t z, uint64_t n, uint64_t N, int logN, int logP
   d.K2 = hgl_mul(K2, G);
   d.rho4096 = hgl_pow(d.rho, 4096);
   d.K3 = hgl_mul(hgl_mul(zn, hgl_inv(z)), hgl_inv(n % GL_P_HOST));  // z^(n-1) / n: kappa = K3 S
+  // rho carries the rank's coset factor and n = E / 2^b for every P: one formula
+  int b = 0;
+  while (b < 3 && (n << (b + 1)) <= M_) b++;
+  const uint64_t rhon = hgl_pow(d.rho, n), wb = hgl_root_2exp((uint32_t)b);
+  uint64_t ws = 1;  // w_{2^b}^s
+  for (int s = 0; s < 8; s++) {
+    d.Gs[s] = 0;
+    if (s >= (1 << b)) continue;
+    const uint64_t ratio = hgl_mul(rhon, ws);
+    uint64_t term = 1;
+    for (int t = 0; t < (1 << b); t++) {
+      d.Gs[s] = hgl_add(d.Gs[s], term);
+      term = hgl_mul(term, ratio);
+    }
+    ws = hgl_mul(ws, wb);
+  }
   return d;
 }
 

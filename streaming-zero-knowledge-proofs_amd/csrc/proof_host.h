@@ -34,9 +34,13 @@ ColumnChallenges column_challenges(Transcript& tr, uint64_t n, int logN);
 // kappa = K3 S. Rank g of 2^logP evaluates the coset 3 w_N^g <w_M>: H's N
 // coefficients fold to M (M >= n): h'_k = [k < n] q_k (3 w_N^g)^k + c' G rho^k,
 // rho = (3/z) w_N^g, G = sum_{t<P} rho^(tM), folded into K2; single device and
-// full_lde (the whole domain, as on one device): rho = 3/z, G = 1
+// full_lde (the whole domain, as on one device): rho = 3/z, G = 1.
+// Gs: the closed-form first LDE stages (DeepPoly, sezkp_internal.h): the rank
+// evaluates E = M (or N) points from n coefficients, b = log(E/n) <= 3, and
+// Gs[s] = sum_{t < 2^b} (rho^n w_{2^b}^s)^t for s < 2^b (0 past that)
 struct DeepConsts {
   uint64_t K1, K2, K3, rho, rho4096;
+  uint64_t Gs[8];
 };
 DeepConsts deep_constants(uint64_t z, uint64_t n, uint64_t N, int logN, int logP, int rank, bool full_lde);
 

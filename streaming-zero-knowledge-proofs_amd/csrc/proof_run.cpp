@@ -36,6 +36,8 @@ ProveOptions ProveOptions::read() {
   o.kernel_events = on("SEZKP_KERNEL_EVENTS");
   o.stage_events = o.kernel_events || on("SEZKP_STAGE_EVENTS");
   o.no_deep_poly = getenv("SEZKP_NO_DEEP_POLY") != nullptr;
+  const char* dpc = getenv("SEZKP_DP_CLOSED");
+  o.dp_closed = !(dpc && dpc[0] == '0' && !dpc[1]);
   if (const char* cap = getenv("SEZKP_DICT_TAB_CAP")) {
     const long v = atol(cap);
     if (v >= 1 && v <= (long)DICT_CAP) o.dict_tab_cap = (uint32_t)v;
@@ -255,7 +257,7 @@ struct ProofRun {
         mroot(manifest_root),
         root_dev(manifest_root == nullptr),
         dist_intt(sharded && ctx.world > 1 && opt.dist_intt),
-        dpoly{ctx.d_dq_rlo, ctx.d_dq_rhi, ctx.d_dq_rhk},
+        dpoly{ctx.d_dq_rlo, ctx.d_dq_rhi, ctx.d_dq_rhk, ctx.d_dq_rhu, ctx.d_dq_gk, false},
         roots((size_t)(k + 1) * 32),
         pos((size_t)NUM_QUERIES * (k + 1)),
         hw_obs((size_t)ctx.n_dict) {}
@@ -552,6 +554,7 @@ struct ProofRun {
       h_chal->rho = d.rho;
       h_chal->rho4096 = d.rho4096;
       h_chal->K3 = d.K3;
+      for (int s = 0; s < 8; s++) h_chal->G[s] = d.Gs[s];
     }
   }
 
@@ -570,6 +573,8 @@ struct ProofRun {
     // alphas, masks and the DEEP constants for the kernels below
     HIP_OR_THROW(hipMemcpyAsync(d_chal, c.h_chal, offsetof(DevChal, beta), hipMemcpyHostToDevice, st));
     const uint64_t dq_per = dq_rows_per_part(row_hi - row_lo);  // base rows per partial sum (k_inv_base WG)
+    // the LDE's first stages in closed form (DeepPoly) where its first pass takes them: the tables follow
+    dpoly.closed = dq && opt.dp_closed && ntt_lde_dpoly_closed(full_lde ? logN : logM, logn, tw);
     if (dq) {
       // the composition's combine (alphas, mask) fused with the DEEP quotient:
       // D_j = C_j / (w^j - z) and the partial sums of f(z) (DeepPoly); the
@@ -618,7 +623,7 @@ struct ProofRun {
       if (dq) {
         fork(st, st2, c.ev_qin);
         ok(launch_q_tables(st2, d_dq_part, logn, full_lde ? logN : logM, d_chal, c.d_dq_rlo, c.d_dq_rhi, c.d_dq_rhk,
-                           dq_per),
+                           c.d_dq_rhu, c.d_dq_gk, dpoly.closed, dq_per),
            "q_tables");
         HIP_OR_THROW(hipEventRecord(c.ev_qout, st2));
       }
@@ -627,7 +632,7 @@ struct ProofRun {
     }
     if (dq && dist_intt)
       ok(launch_q_tables(st, d_dq_part, logn, full_lde ? logN : logM, d_chal, c.d_dq_rlo, c.d_dq_rhi, c.d_dq_rhk,
-                         dq_per),
+                         c.d_dq_rhu, c.d_dq_gk, dpoly.closed, dq_per),
          "q_tables");
     rec(5);
     // ---- coset LDE (prover.rs:137-189, lde.rs:42-97): rank g evaluates on
@@ -882,6 +887,7 @@ struct ProofRun {
     c.host_ms[3] = std::chrono::duration<double, std::milli>(t_end - t_ser).count();
     c.have_plans = true;  // d_dplans: this proof's plans (sezkp_ctx_dict_plans)
     c.pwstat_by_value = st_pw_by_value;
+    c.ldestat_closed = dpoly.closed ? (sp.full_lde ? sp.logN : sp.logM) - sp.logn : 0;
     c.pwstat_units = st_pw_units;
     c.dict.end_proof(du, c.dict_info, hw_obs, st_rebuilt, st_entries);
     return out;

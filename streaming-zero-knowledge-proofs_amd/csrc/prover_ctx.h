@@ -86,6 +86,7 @@ struct ProveOptions {
   // read 0
   bool stage_events = false;
   bool no_deep_poly = false;   // SEZKP_NO_DEEP_POLY: the per-point DEEP division
+  bool dp_closed = true;       // SEZKP_DP_CLOSED=0: the LDE's first pass loads the DEEP polynomial point by point
   uint32_t dict_tab_cap = DICT_CAP;  // largest dictionary table above level 0 (entries; SEZKP_DICT_TAB_CAP, for A/Bs)
   // test hook: plan the dictionary columns as on a device with 2^v rows
   // (SEZKP_TEST_DICT_PLAN_ROWS_LOG=<v>), so small traces run the level / lane
@@ -424,6 +425,7 @@ struct sezkp_ctx {
   // (sezkp_ctx_pw_table_stats; TraceDev::pw_stat)
   std::vector<uint32_t> pw_blk_cols;
   uint32_t pwstat_by_value = 0;
+  int32_t ldestat_closed = 0;  // the last proof's closed-form first LDE stages (sezkp_ctx_lde_closed_stages)
   uint64_t pwstat_units = 0;
   uint32_t* d_dlev = nullptr;        // dictionary columns' chunk levels 6..9 (openings)
   std::vector<uint32_t> dict_of;     // column -> dictionary index or NO_DICT
@@ -442,6 +444,7 @@ struct sezkp_ctx {
   uint64_t* d_base = nullptr;
   ComposeTerms Tm{};  // per-row composition sums (k_compose_terms, side stream)
   uint64_t *d_dq_part = nullptr, *d_dq_rlo = nullptr, *d_dq_rhi = nullptr, *d_dq_rhk = nullptr;  // DeepPoly
+  uint64_t *d_dq_rhu = nullptr, *d_dq_gk = nullptr;  // DeepPoly, the closed-form first stages
   uint64_t* d_lde = nullptr;
   uint64_t* d_fri = nullptr;
   uint32_t* d_roots = nullptr;

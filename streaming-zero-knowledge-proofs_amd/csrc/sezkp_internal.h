@@ -45,6 +45,11 @@ struct NttPassArgs {
   const uint64_t* dp_rhi;
   const uint64_t* dp_rhk;
   int dp_logN;
+  // closed-form first stages (k_ntt4's narrow first pass, b = dp_logN - log_src
+  // in 1..3; null = the load above): after its first b stages group g holds
+  // x[2^b g + s] = qv_g + r^e0 gk[s], e0 = bitrev(g), r^e0 = rhu[e0 >> 12] rlo[e0 & 4095]
+  const uint64_t* dp_gk;
+  const uint64_t* dp_rhu;
   // out-of-place DIF store (null = in place); nat_out: the last (narrow) DIF
   // pass writes position p to out[bitrev_{nat_logN}(p)] * out_scale, i.e. the
   // transform leaves in natural order without a bit-reversal pass
@@ -80,10 +85,23 @@ struct DeepFuse {
 // with kappa = f(z) z^(n-1) / (1 - z^n) = K3 S. The INTT runs on D and the
 // LDE's first pass subtracts kappa r^k for k < n; f(z) (the partial sums) is
 // needed only there, so sharded ranks gather it with the INTT coefficients.
+//
+// The first b = log(E/n) DIT stages of the E-point LDE in closed form: they
+// combine the 2^b inputs of one group (positions 2^b g + s), whose
+// coefficients are e0 + t n (t = bitrev_b(s), e0 = bitrev(g)). The q part and
+// the kappa correction have one non-zero input per group (t = 0), which the
+// stages copy into every slot; the S part is geometric with the ratio r^n, so
+// slot s ends as c' r^e0 G[s] with G[s] = sum_{t < 2^b} (r^n w_{2^b}^s)^t, 2^b
+// constants per proof (deep_constants). Together
+//   x[2^b g + s] = q_e0 3^e0 (coset factor) + r^e0 (c' G[s] - kappa),
+// and the pass runs its remaining stages only (fft_dit_regs<M1, INV, b>).
 struct DeepPoly {
   const uint64_t* rlo;  // 4096 entries: r^t
   const uint64_t* rhi;  // N >> 12 entries: c' r^(4096 t)
   const uint64_t* rhk;  // max(1, n >> 12) entries: kappa r^(4096 t)
+  const uint64_t* rhu;  // max(1, n >> 12) entries: r^(4096 t)
+  const uint64_t* gk;   // 8 entries: c' G[s] - kappa (s < 2^b)
+  bool closed;          // k_q_tables wrote rlo / rhu / gk (else rlo / rhi / rhk)
 };
 // over a block of base rows [row0, row0 + nrows) (row0 a multiple of per):
 // D_j = C_j / (w^j - z) into D, C_j = compose_value of the row's terms (one
@@ -95,9 +113,11 @@ uint64_t dq_rows_per_part(uint64_t nrows);
 hipError_t launch_inv_base(hipStream_t st, const ComposeTerms& Tm, uint64_t* D, uint64_t* partial, int logn,
                            const DevChal* ch, const NttTables& T, uint64_t row0, uint64_t nrows, uint64_t per);
 // once every partial of the n rows is in `partial`: f(z) = K1 S, the DeepPoly
-// tables rlo / rhi / rhk (K1, K2, K3, rho, rho^4096 from ch)
+// tables rlo / rhi / rhk, or with `closed` rlo / rhu / gk (K1, K2, K3, rho,
+// rho^4096, G from ch)
 hipError_t launch_q_tables(hipStream_t st, const uint64_t* partial, int logn, int logN, const DevChal* ch,
-                           uint64_t* rlo, uint64_t* rhi, uint64_t* rhk, uint64_t per);
+                           uint64_t* rlo, uint64_t* rhi, uint64_t* rhk, uint64_t* rhu, uint64_t* gk, bool closed,
+                           uint64_t per);
 
 // The transforms (ntt_run.cpp): each makes its request, plans it (ntt_plan.h)
 // and walks the plan; a request no kernel takes fails before any launch.
@@ -113,6 +133,10 @@ hipError_t ntt_dit(hipStream_t st, uint64_t* a, int logN, bool inverse, const Nt
                    const uint64_t* src, int log_src, uint64_t inv_n, uint64_t coset_e = 0,
                    const DeepFuse* deep = nullptr, bool* fused = nullptr, const DeepPoly* dpoly = nullptr,
                    int src_logP = 0);
+// whether the DEEP-polynomial LDE of 2^logN points from 2^log_src coefficients
+// takes the closed-form first stages (DeepPoly): its first pass is k_ntt4's
+// plain narrow one and 1 <= logN - log_src <= 3
+bool ntt_lde_dpoly_closed(int logN, int log_src, const NttTables& T);
 // one planned pass (ntt_plan.h) to its kernel: the 256-lane forms
 // (ntt_pass.hip) and the 512-lane ones (ntt_pass512.hip); false = not a form
 // of that unit, nothing launched. pass_twiddles: the pass-twiddle table of a
@@ -361,6 +385,7 @@ struct DevChal {
   uint64_t mask[4];                 // derive_mask_coeffs (masking.rs:56-79)
   uint64_t z, zn, K1, K2, rho, rho4096;  // OOD point (nudged) and the DEEP-polynomial constants
   uint64_t K3;                      // z^(n-1) / n: kappa = K3 S (DeepPoly, the q correction)
+  uint64_t G[8];                    // G[s] of the closed-form first LDE stages (DeepPoly), 0 past 2^b
   uint64_t beta[FS_MAX_BETAS];      // derive_betas_for_fri (params.rs:109-119)
 };
 

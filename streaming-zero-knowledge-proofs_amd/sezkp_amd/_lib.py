@@ -49,6 +49,7 @@ EXPORTS = [
     "sezkp_ctx_ingest_blocks_cbor", "sezkp_ctx_upload_ingested", "sezkp_ctx_upload_blocks_cbor",
     "sezkp_ctx_decode_blocks_cbor", "sezkp_stark_v1_prove_blocks_cbor", "sezkp_blocks_cbor_head",
     "sezkp_ctx_blocks_ingest_stats",
+    "sezkp_ctx_lde_closed_stages",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -203,6 +204,7 @@ def _load():
     L.sezkp_ctx_pw_table_stats.argtypes = [C.c_void_p, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                            C.POINTER(C.c_uint64)]
     L.sezkp_ctx_head_wide_stats.argtypes = [C.c_void_p, C.POINTER(HeadWideInfo), C.c_int32]
+    L.sezkp_ctx_lde_closed_stages.argtypes = [C.c_void_p, C.POINTER(C.c_int32)]
     L.sezkp_gl_ntt.argtypes = [C.c_void_p, C.c_void_p, C.c_uint32, C.c_int32, C.c_void_p]
     L.sezkp_gl_coset_lde_deep.argtypes = [C.c_void_p, C.c_uint32, C.c_uint32, C.c_uint64, C.c_uint64, C.c_void_p,
                                           C.c_void_p, C.c_void_p]

@@ -627,6 +627,17 @@ class ProverContext:
             raise SezkpError(rc, "pw_table_stats: a proof is in flight on this context (or the context is closed)")
         return {"cols_by_value": by_value.value, "cols_by_block": by_block.value, "units_built": units.value}
 
+    def lde_closed_stages(self) -> int:
+        """The butterfly stages the last completed prove's first LDE pass formed
+        in closed form (sezkp_ctx_lde_closed_stages): 1..3, or 0 for the
+        point-by-point load (SEZKP_DP_CLOSED=0, a rank evaluating as many
+        points as the trace has rows) and the per-point DEEP division."""
+        b = C.c_int32(0)
+        rc = lib.sezkp_ctx_lde_closed_stages(self._h, C.byref(b))
+        if rc != 0:
+            raise SezkpError(rc, "lde_closed_stages: a proof is in flight on this context (or the context is closed)")
+        return b.value
+
     def dist_ntt(self, local, scratch=None, inverse: bool = False, sync: bool = True):
         """Distributed four-step NTT of n = world * local.numel() points, in
         place on `local` (a device u64/i64 tensor; layouts in sezkp_stark.h,

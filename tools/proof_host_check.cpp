@@ -120,9 +120,11 @@ int main(int argc, char** argv) {
       const bool full_lde = P > 1 && shape_of_logn(tau, 1, 12 + logP, rank, logP, true).full_lde;
       const DeepConsts d = deep_constants(ch.z, s.n, s.N, s.logN, logP, rank, full_lde);
       printf("%s{\"P\": %d, \"rank\": %d, \"full_lde\": %d, \"K1\": %llu, \"K2\": %llu, \"K3\": %llu, \"rho\": %llu, "
-             "\"rho4096\": %llu}",
+             "\"rho4096\": %llu, ",
              sep, P, rank, (int)full_lde, (unsigned long long)d.K1, (unsigned long long)d.K2, (unsigned long long)d.K3,
              (unsigned long long)d.rho, (unsigned long long)d.rho4096);
+      put_list("Gs", d.Gs, 8);
+      printf("}");
       sep = ", ";
       p = strchr(p, ',');
       if (p) p++;
