@@ -12,7 +12,7 @@
 //    sibling is its own sibling)
 // One lane per digest: 8-byte loads, 32-byte (2 x 16 B) stores, consecutive
 // lanes on consecutive digests. These are HBM/VALU-streaming kernels; the
-// prover's fused versions live in merkle.hip.
+// prover's fused versions live in merkle_tree.hip, fri_forest.hip and fri_paths.hip.
 #include "col_leaf.h"
 
 namespace sezkp {

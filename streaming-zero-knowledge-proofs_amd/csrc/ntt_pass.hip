@@ -199,7 +199,7 @@ __global__ void __launch_bounds__(NTT_THREADS) k_ntt_pass(NttPassArgs P) {
 //     position q*F1 + q' (k_hi = rev_M1(q')).
 
 // Fused DEEP (last forward DIT pass of the LDE only): out_i = y_i / (x_i - z),
-// x_i = 3 w_N^(g + P i) (merkle.hip k_deep, lde.rs:76-93). A thread's F2
+// x_i = 3 w_N^(g + P i) (deep_div.hip k_deep, lde.rs:76-93). A thread's F2
 // outputs sit F1 << sL apart, so consecutive x differ by w_F2 (a power of
 // two: a shift); one Montgomery batch inversion per workgroup (4096 points).
 template <int F, class Emit>

@@ -419,9 +419,6 @@ hipError_t launch_compose_terms(hipStream_t st, const TraceDev& T, const Compose
                                 uint64_t nrows);
 hipError_t launch_compose_combine(hipStream_t st, const ComposeTerms& Tm, const DevChal* ch, const NttTables& tw,
                                   int logn, uint64_t* out, uint64_t row0, uint64_t nrows);
-// DEEP divide of y[j] at x = shift * w_{2^logN}^(g + (j << logP)) (logP = 0, g = 0: natural layout)
-hipError_t launch_deep(hipStream_t st, uint64_t* y, int logN, uint64_t z, const NttTables& tw, int logP = 0,
-                       uint32_t g = 0, uint64_t shift = 3);
 // a[p] *= base^bitrev_logn(p) (tables lo[2048] | hi[max(1, n >> 11)] in `scratch`)
 hipError_t launch_scale_pow_bitrev(hipStream_t st, uint64_t* a, int logn, uint64_t base, uint64_t* scratch);
 // kernel-level ABI helpers (api_kernels.hip); digests are 8 u32 words
@@ -445,50 +442,22 @@ struct VerifyJobDev;
 struct VerifyLabel;
 hipError_t launch_verify_chains(hipStream_t st, const uint8_t* bytes, const VerifyJobDev* jobs, const uint8_t* roots,
                                 const VerifyLabel* labels, uint32_t njobs, uint32_t* result);
+// ---- deep_div.hip
+// DEEP divide of y[j] at x = shift * w_{2^logN}^(g + (j << logP)) (logP = 0, g = 0: natural layout)
+hipError_t launch_deep(hipStream_t st, uint64_t* y, int logN, uint64_t z, const NttTables& tw, int logP = 0,
+                       uint32_t g = 0, uint64_t shift = 3);
+// ---- shard_layout.hip
 // Sharded LDE layout change (proof_run.cpp, enqueue_B): cyclic coset
 // values of rank g (index g + P*j) <-> runs of S = 2^12 consecutive indices.
 hipError_t launch_cyc_pack(hipStream_t st, const uint64_t* cyc, uint64_t* send, uint64_t M, int logP);
 hipError_t launch_cyc_unpack(hipStream_t st, const uint64_t* recv, uint64_t* local, uint64_t M, int logP);
-// gathered[d][k1] (run roots of rank d) -> level-12 node k1*P + d of `cap`
 // rank g's runs of 4096 (local index k1 S + t = global (k1 P + g) S + t) out
 // of the whole N-point LDE (sharded P = 2)
 hipError_t launch_runs_extract(hipStream_t st, const uint64_t* full, uint64_t* local, uint64_t M, int logP,
                                uint32_t g);
-constexpr int RR_BATCH_MAX = 40;
-struct RunRootsBatch {
-  const uint32_t* gathered[RR_BATCH_MAX];
-  TreeDev cap[RR_BATCH_MAX];
-  uint64_t nrun[RR_BATCH_MAX];  // runs per rank
-  int n, logP;
-};
-hipError_t launch_runroots_scatter_multi(hipStream_t st, const RunRootsBatch& B);
-hipError_t launch_runroots_scatter(hipStream_t st, const uint32_t* gathered, TreeDev cap, uint64_t nrun_per_rank,
-                                   int logP);
-// dbeta != null: the fold challenge is read from device memory instead of `beta`
-hipError_t launch_leaf_subtree(hipStream_t st, const uint64_t* in, uint64_t* out_vals, int logLen, int fold,
-                               uint64_t beta, TreeDev tree, const uint64_t* dbeta = nullptr);
-hipError_t launch_tree_upper(hipStream_t st, TreeDev* trees, int ntrees_same_shape, uint64_t tree_stride_nodes,
-                             uint64_t root_stride_words, int from_level);
-// A FRI layer as seen by the path kernel. Unsharded: vals/tree hold the
-// whole layer and cap == tree. Sharded run layers: vals/tree are this rank's
-// runs (global index i -> local ((i >> (12+logP)) << 12) | (i & 4095), tree
-// levels < 12 valid) and cap holds levels >= 12 with global indices.
-struct FriLayerDev {
-  const uint64_t* vals;
-  TreeDev tree;
-  TreeDev cap;
-  uint32_t sharded;
-  uint32_t logP;
-};
-hipError_t launch_upper_jobs(hipStream_t st, const UpperJob* d_jobs, int njobs);
-
-// stop: highest level the WG reduces to (L16_LOG = its run root; LSTORE_FRI
-// leaves levels 7..12 to the upper jobs, whose lanes are all busy)
-// wg_log: leaves per WG (L16_LOG, or L16S_LOG for trees too small to fill
-// the chip with 4096-leaf WGs); stop <= wg_log
-hipError_t launch_layer16(hipStream_t st, const uint64_t* in, uint64_t* out_vals, int logLen, int fold, uint64_t beta,
-                          TreeDev tree, int stop = L16_LOG, const uint64_t* dbeta = nullptr, int wg_log = L16_LOG);
-// Fold chain kernel (values only) and the one-launch forest of layer trees.
+// ---- fri_fold.hip
+// Fold chain kernel (values only); dbeta != null: the fold challenge is read
+// from device memory instead of `beta`
 hipError_t launch_fold(hipStream_t st, const uint64_t* in, uint64_t* out, int logLen, uint64_t beta,
                        const uint64_t* dbeta = nullptr);
 // F = 2..FOLD_MAX folds in one pass (k_foldm): out[m-1] = layer r + m, beta[m-1] its challenge
@@ -498,6 +467,22 @@ struct FoldOuts {
   const uint64_t* beta;  // device: beta[m - 1] folds layer r + m - 1 (the pass's first challenge)
 };
 hipError_t launch_foldm(hipStream_t st, const uint64_t* in, const FoldOuts& outs, int F, int logLenF);
+// ---- merkle_tree.hip
+// the whole tree of a layer (>= 4096 leaves: launch_layer16, then the upper
+// levels); fold, beta, dbeta as launch_fold, the folded layer goes to out_vals
+hipError_t launch_leaf_subtree(hipStream_t st, const uint64_t* in, uint64_t* out_vals, int logLen, int fold,
+                               uint64_t beta, TreeDev tree, const uint64_t* dbeta = nullptr);
+hipError_t launch_tree_upper(hipStream_t st, TreeDev* trees, int ntrees_same_shape, uint64_t tree_stride_nodes,
+                             uint64_t root_stride_words, int from_level);
+hipError_t launch_upper_jobs(hipStream_t st, const UpperJob* d_jobs, int njobs);
+// ---- fri_forest.hip
+// stop: highest level the WG reduces to (L16_LOG = its run root; LSTORE_FRI
+// leaves levels 7..12 to the upper jobs, whose lanes are all busy)
+// wg_log: leaves per WG (L16_LOG, or L16S_LOG for trees too small to fill
+// the chip with 4096-leaf WGs); stop <= wg_log
+hipError_t launch_layer16(hipStream_t st, const uint64_t* in, uint64_t* out_vals, int logLen, int fold, uint64_t beta,
+                          TreeDev tree, int stop = L16_LOG, const uint64_t* dbeta = nullptr, int wg_log = L16_LOG);
+// the one-launch forest of layer trees
 struct ForestLayer {
   const uint64_t* vals;
   TreeDev tree;
@@ -520,9 +505,22 @@ hipError_t launch_fri_tail(hipStream_t st, const TailArgs& a);
 hipError_t launch_forest16(hipStream_t st, const ForestLayer* d_layers, int nlayers, uint32_t total_wgs,
                            const TailArgs* tail = nullptr, uint64_t* tailbuf = nullptr, uint32_t wg_base = 0,
                            int wg_log = L16_LOG);
+// ---- fri_paths.hip
+// A FRI layer as seen by the path kernel. Unsharded: vals/tree hold the
+// whole layer and cap == tree. Sharded run layers: vals/tree are this rank's
+// runs (global index i -> local ((i >> (12+logP)) << 12) | (i & 4095), tree
+// levels < 12 valid) and cap holds levels >= 12 with global indices.
+struct FriLayerDev {
+  const uint64_t* vals;
+  TreeDev tree;
+  TreeDev cap;
+  uint32_t sharded;
+  uint32_t logP;
+};
 // requests: (layer, index, ordinal in the proof's FRI records) triples
 hipError_t launch_fri_paths(hipStream_t st, const FriLayerDev* d_layers, const uint32_t* d_req, int nreq,
                             const ProofLayout& P);
+// ---- col_open.hip
 // requests: OPEN_REQ_WORDS words each
 hipError_t launch_col_open(hipStream_t st, const TraceDev& T, const ColTemplate* d_tmpl, const uint32_t* outer_nodes,
                            uint64_t outer_stride_nodes, int logChunks, const uint32_t* d_req, int nreq,

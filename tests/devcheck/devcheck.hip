@@ -340,5 +340,22 @@ int sezkp_dc_upper_jobs(uint64_t nodes, uint64_t root, int logLen, int lstore, i
   if (njobs) *njobs = total;
   return 0;
 }
+// the whole tree of a layer of any size; in, out, fold, beta, dbeta as sezkp_dc_layer16
+int sezkp_dc_leaf_subtree(uint64_t in, uint64_t out, int logLen, int fold, uint64_t beta, uint64_t dbeta,
+                          uint64_t nodes, uint64_t root, int lstore) {
+  if (logLen < 0 || logLen > 24) return (int)hipErrorInvalidValue;
+  return dc_done(launch_leaf_subtree(nullptr, reinterpret_cast<const uint64_t*>(in), reinterpret_cast<uint64_t*>(out),
+                                     logLen, fold, beta, tree_of(nodes, root, logLen, lstore),
+                                     reinterpret_cast<const uint64_t*>(dbeta)));
+}
+// levels from + 1 .. logLen of ntrees trees of one shape from their stored
+// level `from`: tree t's nodes start tree_stride nodes after tree t - 1's,
+// its root root_stride words after
+int sezkp_dc_tree_upper(uint64_t nodes, uint64_t root, int logLen, int lstore, int ntrees, uint64_t tree_stride,
+                        uint64_t root_stride, int from) {
+  if (from < lstore || from > logLen || logLen > 30 || ntrees < 1 || ntrees > 16) return (int)hipErrorInvalidValue;
+  TreeDev T = tree_of(nodes, root, logLen, lstore);
+  return dc_done(launch_tree_upper(nullptr, &T, ntrees, tree_stride, root_stride, from));
+}
 
 }  // extern "C"

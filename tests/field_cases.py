@@ -328,6 +328,8 @@ def load_devcheck(path):
         "sezkp_dc_forest16": [i32, ptr, ptr, ptr, ptr, ptr, i32, i32, i32, u64, i32, u64, ptr, ptr, ptr, i32, u64],
         "sezkp_dc_layer16": [u64, u64, i32, i32, u64, u64, u64, u64, i32, i32, i32],
         "sezkp_dc_upper_jobs": [u64, u64, i32, i32, i32, i32, u64, u64, i32, ptr],
+        "sezkp_dc_leaf_subtree": [u64, u64, i32, i32, u64, u64, u64, u64, i32],
+        "sezkp_dc_tree_upper": [u64, u64, i32, i32, i32, u64, u64, i32],
     }
     for name, args in sig.items():
         fn = getattr(lib, name)

@@ -137,7 +137,8 @@ def test_butterfly_references_agree():
 def test_devcheck_library_loads_and_exports():
     assert os.path.exists(DEVCHECK), "lib/libsezkp_devcheck.so is not built (make in the package)"
     lib = F.load_devcheck(DEVCHECK)  # getattr on every entry point: a missing export raises here
-    assert len(lib.entry_points) == 15
+    assert len(lib.entry_points) == 17
     exported = set(lib.entry_points)
     assert {"sezkp_dc_unary", "sezkp_dc_mul_pow2_ct", "sezkp_dc_fft_regs", "sezkp_dc_foldm", "sezkp_dc_fri_tail",
-            "sezkp_dc_forest16", "sezkp_dc_layer16", "sezkp_dc_upper_jobs"} <= exported
+            "sezkp_dc_forest16", "sezkp_dc_layer16", "sezkp_dc_upper_jobs", "sezkp_dc_leaf_subtree",
+            "sezkp_dc_tree_upper"} <= exported

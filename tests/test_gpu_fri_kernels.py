@@ -1,4 +1,5 @@
-"""The FRI fold / tail / forest / layer kernels of csrc/merkle.hip driven
+"""The FRI fold / tail / forest / layer / tree kernels of csrc/fri_fold.hip,
+fri_forest.hip and merkle_tree.hip driven
 directly through the product's own launchers (lib/libsezkp_devcheck.so), with
 boundary values and boundary challenges: what the prover feeds them only by
 chance. Values come from the EDGE set with runs of p - 1; betas are the
@@ -349,3 +350,67 @@ def test_upper_jobs_from_gathered_roots(gpu_ok, dc, logLen, frm):
         nodes, root = tree.nodes.host().tobytes(), tree.root.host().tobytes()
         assert nodes == upper, "cap levels %d..%d (logP=%d)" % (frm, logLen, logP)
         assert root == upper[-32:]
+
+
+# ------------------------------------------- whole trees and upper levels
+@pytest.mark.parametrize("lstore", [LSTORE_FRI, 0])
+@pytest.mark.parametrize("fold_in", [0, 1])
+@pytest.mark.parametrize("logLen", [0, 1, 2, 3, 8, 9, 10, 11, 12, 13])
+def test_leaf_subtree_every_level(gpu_ok, dc, logLen, fold_in, lstore):
+    """launch_leaf_subtree: k_leaf_subtree with 1, 2 (its scalar branch) and 4
+    leaves per lane, fewer than 256 active lanes (2^8), exactly one workgroup
+    (2^10), two workgroups and one upper launch (2^11), and the hand-over to
+    k_layer16<4> alone (2^12) and with an upper launch (2^13). Every stored
+    level and the root; with the fused fold also the folded values, the
+    challenge by value and from device memory."""
+    torch = gpu_ok
+    src = values((2 if fold_in else 1) << logLen, 170 + logLen)
+    d_src = dev_u64(torch, src)
+    picks = [BETAS[(logLen + lstore) % len(BETAS)], BETAS[(logLen + lstore + 3) % len(BETAS)]] if fold_in else [0]
+    for by_dev, beta in enumerate(picks):
+        want = fold(src, beta) if fold_in else src
+        out = Buf(torch, (1 << logLen) if fold_in else 1, torch.int64)
+        tree = Tree(torch, logLen, lstore)
+        d_beta = dev_u64(torch, [beta])
+        assert dc.sezkp_dc_leaf_subtree(d_src.data_ptr(), out.ptr, logLen, fold_in, 0 if by_dev else beta,
+                                        d_beta.data_ptr() if by_dev else 0, tree.nodes.ptr, tree.root.ptr,
+                                        lstore) == 0
+        what = "launch_leaf_subtree logLen=%d fold=%d lstore=%d beta=%#x by_dev=%d" % (logLen, fold_in, lstore, beta,
+                                                                                     by_dev)
+        if fold_in:
+            assert out.host().tolist() == list(want), what + ": folded values"
+        else:
+            assert (out.host() == out.fill).all(), what + ": no fold, but values were written"
+        tree.check(want, what)
+        if logLen < lstore:
+            assert (tree.nodes.host() == tree.nodes.fill).all(), what + ": no stored level, but nodes were written"
+
+
+@pytest.mark.parametrize("logLen,frm,ntrees", [(6, 6, 1), (7, 6, 2), (16, 6, 1), (17, 6, 1)])
+def test_tree_upper_from_stored_level(gpu_ok, dc, logLen, frm, ntrees):
+    """launch_tree_upper from random level-`frm` nodes: the single-node root
+    job, one parent (two trees of one shape, their nodes and roots spaced by
+    strides that leave gaps), exactly one step of 10 levels, two launches."""
+    torch = gpu_ok
+    import oracle_ctypes as O
+    rng = random.Random(180 + logLen)
+    cnt, stored = 1 << (logLen - frm), stored_nodes(logLen, frm)
+    tstride, rstride = (stored + 3, 12) if ntrees > 1 else (0, 0)  # nodes, words
+    nodes = Buf(torch, 8 * (tstride * (ntrees - 1) + stored), torch.int32)
+    roots = Buf(torch, rstride * (ntrees - 1) + 8, torch.int32)
+    want = []
+    for t in range(ntrees):
+        level = b"".join(rng.randbytes(32) for _ in range(cnt))
+        want.append(O.merkle_nodes(level))  # levels frm .. logLen, bottom -> top: the stored layout
+        assert len(want[t]) == 32 * stored
+        nodes.t[8 * tstride * t:8 * (tstride * t + cnt)] = torch.from_numpy(
+            np.frombuffer(level, dtype=np.int32).copy()).cuda()
+    assert dc.sezkp_dc_tree_upper(nodes.ptr, roots.ptr, logLen, frm, ntrees, tstride, rstride, frm) == 0
+    got, got_roots = nodes.host(), roots.host()
+    for t in range(ntrees):
+        what = "launch_tree_upper logLen=%d from=%d tree %d" % (logLen, frm, t)
+        assert got[8 * tstride * t:8 * (tstride * t + stored)].tobytes() == want[t], what + ": levels"
+        assert got_roots[rstride * t:rstride * t + 8].tobytes() == want[t][-32:], what + ": root"
+    for t in range(ntrees - 1):  # the gaps between the trees and between the roots
+        assert (got[8 * (tstride * t + stored):8 * tstride * (t + 1)] == nodes.fill).all()
+        assert (got_roots[rstride * t + 8:rstride * (t + 1)] == roots.fill).all()

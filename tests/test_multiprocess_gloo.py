@@ -68,7 +68,8 @@ def test_host_collectives_gloo(world):
 
 def _layout_worker(rank, world, port, log_n, q):
     """numpy model of the sharded LDE/FRI layout (same index maps as
-    k_cyc_pack / k_cyc_unpack / k_runroots_scatter / the path ownership)."""
+    k_cyc_pack / k_cyc_unpack / the cap's read of the gathered run roots
+    (upper_load) / the path ownership)."""
     sys.path[:0] = [PKG, ORACLE]
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port))
     import numpy as np
