@@ -556,6 +556,60 @@ typedef struct sezkp_blocks_ingest_info {
  * flight, or before the context's first decode call. */
 int32_t sezkp_ctx_blocks_ingest_stats(const sezkp_ctx* ctx, sezkp_blocks_ingest_info* out);
 
+/* ------------------------------------------------ block and trace files encoded on the device
+ * sezkp_blocks_encode_cbor and sezkp_trace_encode_cbor push bytes on one host
+ * thread, O(t) behind the proof. These write the same files on the context's
+ * GPU from step arrays that are in device memory already (the active trace
+ * image, arrays produced on the GPU) or are copied there, and bring home only
+ * the file's bytes, byte for byte what the host encoders write
+ * (csrc/cbor_emit_plan.h). The file image lives in device memory of the
+ * context's own, apart from the ingest buffers: a pending
+ * sezkp_ctx_ingest_blocks_cbor survives an encode, and an encode touches
+ * neither the trace image, the upload workspace, the dictionary tables nor a
+ * proof's state. *out: library-allocated, sezkp_buf_free.
+ * SEZKP_CBOR_ENCODE_HOST=1 (read per call) makes all three run the host
+ * encoder on arrays read back: the same bytes, path SEZKP_INGEST_HOST.
+ * Null arguments, tau > 255 and shape errors (a step_start that does not
+ * start at 0 or decreases) are SEZKP_E_INVALID before any device call; a
+ * device allocation that fails is SEZKP_E_DEVICE; the context stays usable.
+ * Out of scope: JSONL output, output left in device memory, sharded contexts,
+ * non-zero pre_tags / post_tags, a meta other than null. */
+/* The blocks file of the active trace image: what sezkp_ctx_trace_blocks
+ * followed by sezkp_blocks_encode_cbor returns, with no step copied to the
+ * host except as file bytes. Preconditions and errors as for
+ * sezkp_ctx_trace_blocks (sharded contexts: SEZKP_E_INVALID). */
+int32_t sezkp_ctx_encode_trace_blocks_cbor(sezkp_ctx* ctx, sezkp_buf* out, char* err, size_t err_len);
+/* Any block view: non-uniform step_start, blocks of zero steps, any field
+ * values. The step arrays may be host memory or device memory of the
+ * context's device (hipPointerGetAttributes decides, per array); the block
+ * tables and step_start are host memory. Needs no uploaded trace. */
+int32_t sezkp_ctx_encode_blocks_cbor(sezkp_ctx* ctx, const sezkp_block_view* blocks, sezkp_buf* out, char* err,
+                                     size_t err_len);
+/* The TraceFile (version 1, meta null) of `trace`, host or device arrays; b is
+ * ignored. trace = NULL: the active trace image's (preconditions as for
+ * sezkp_ctx_trace_blocks). */
+int32_t sezkp_ctx_encode_trace_cbor(sezkp_ctx* ctx, const sezkp_trace_view* trace, sezkp_buf* out, char* err,
+                                    size_t err_len);
+/* What the context's last encode call did (path: SEZKP_INGEST_DEVICE /
+ * SEZKP_INGEST_HOST). */
+#define SEZKP_ENCODE_R_NONE 0u    /* the device wrote the file */
+#define SEZKP_ENCODE_R_FORCED 1u  /* SEZKP_CBOR_ENCODE_HOST=1 */
+#define SEZKP_ENCODE_R_EMPTY 2u   /* a block file of no blocks: the one byte 80, from the host */
+typedef struct sezkp_encode_info {
+  uint32_t path;
+  uint32_t reason;    /* SEZKP_ENCODE_R_*: why the host wrote the file */
+  uint64_t bytes;     /* the file's length */
+  uint64_t t;         /* steps, tapes and blocks of what was encoded (a TraceFile: n_blocks 0) */
+  uint32_t tau;
+  uint32_t n_blocks;
+  double ms_kernels;  /* HIP events: the length and emit kernels; the copy home; 0 when not run */
+  double ms_d2h;
+  double ms_host;     /* the host encoder's wall time with its readback; 0 when it did not run */
+} sezkp_encode_info;
+/* SEZKP_OK, or SEZKP_E_INVALID for a null argument, while a proof is in
+ * flight, or before the context's first encode call. */
+int32_t sezkp_ctx_encode_stats(const sezkp_ctx* ctx, sezkp_encode_info* out);
+
 /* ------------------------------------------------ full-trace AIR audit
  * Does the committed trace satisfy the AIR, on every row? The reference
  * verifier recomputes the composition (air.rs:49-136) only on its 30 opened

@@ -746,6 +746,37 @@ int32_t sezkp_ctx_blocks_ingest_stats(const sezkp_ctx* cctx, sezkp_blocks_ingest
   return SEZKP_OK;
 }
 
+// ---- block and trace files encoded on the device (ctx_encode.cpp)
+int32_t sezkp_ctx_encode_trace_blocks_cbor(sezkp_ctx* ctx, sezkp_buf* out, char* err, size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->encode_trace_blocks_cbor(out);
+  });
+}
+int32_t sezkp_ctx_encode_blocks_cbor(sezkp_ctx* ctx, const sezkp_block_view* blocks, sezkp_buf* out, char* err,
+                                     size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !blocks || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->encode_blocks_cbor(*blocks, out);
+  });
+}
+int32_t sezkp_ctx_encode_trace_cbor(sezkp_ctx* ctx, const sezkp_trace_view* trace, sezkp_buf* out, char* err,
+                                    size_t err_len) {
+  return guarded(err, err_len, SEZKP_E_NOMEM, [&] {
+    if (!ctx || !out) throw Err{SEZKP_E_INVALID, "null argument"};
+    require_idle(ctx);
+    ctx->encode_trace_cbor(trace, out);
+  });
+}
+int32_t sezkp_ctx_encode_stats(const sezkp_ctx* cctx, sezkp_encode_info* out) {
+  sezkp_ctx* ctx = const_cast<sezkp_ctx*>(cctx);
+  if (!ctx || !out || ctx->busy() || !ctx->enc.have_info) return SEZKP_E_INVALID;
+  *out = ctx->enc.info;
+  return SEZKP_OK;
+}
+
 // The argument checks come before any device is touched. A file without the
 // canonical head would be decoded on the host anyway: it is decoded here,
 // once, before a device is opened (so its refusal needs none), and its blocks

@@ -14,7 +14,8 @@
 //                               start A2 68 "input_mv" (step candidates) and,
 //                               at KINDS = 2, AE 67 "version" (block candidates);
 //   k_cbor_tile_scan            one workgroup, once per kind: the exclusive scan
-//                               of the tile counts and the number of candidates;
+//                               of the tile counts and the number of candidates
+//                               (cbor_scan_dev.h, shared with the encoder);
 //   k_cbor_marks<KINDS, true>   the same marks again, now stored in file order
 //                               (the first cap of each kind): wave64 ballots
 //                               and popcounts give a lane its place in the
@@ -38,6 +39,7 @@
 #include <hip/hip_runtime.h>
 
 #include "blocks_cbor_plan.h"
+#include "cbor_scan_dev.h"
 #include "sezkp_internal.h"
 
 namespace sezkp {
@@ -100,51 +102,6 @@ __global__ void __launch_bounds__(TC_THREADS) k_cbor_marks(CborSpan s, uint64_t 
   }
 }
 
-// offs[i] = the sum of the counts before i; *total = all of them (candidates
-// per tile, steps per block)
-static __global__ void __launch_bounds__(TC_THREADS) k_cbor_tile_scan(const uint32_t* __restrict__ counts, uint64_t ntiles,
-                                                                      uint64_t* __restrict__ offs, uint64_t* total_out) {
-  __shared__ unsigned long long sh[TC_THREADS / 64];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  constexpr uint32_t PER = TRACE_CBOR_SCAN_PASS / TRACE_CBOR_THREADS;
-  unsigned long long carry = 0;
-  for (uint64_t base = 0; base < ntiles; base += TRACE_CBOR_SCAN_PASS) {
-    const uint64_t i0 = base + (uint64_t)threadIdx.x * PER;
-    uint32_t c[PER];
-    unsigned long long sum = 0;
-#pragma unroll
-    for (uint32_t k = 0; k < PER; k++) {
-      c[k] = i0 + k < ntiles ? counts[i0 + k] : 0u;
-      sum += c[k];
-    }
-    unsigned long long x = sum;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const unsigned long long y = __shfl_up(x, o, 64);
-      if (lane >= o) x += y;
-    }
-    if (lane == 63) sh[wave] = x;
-    __syncthreads();
-    unsigned long long before = 0, total = 0;
-#pragma unroll
-    for (int w = 0; w < TC_THREADS / 64; w++) {
-      const unsigned long long v = sh[w];
-      if (w < wave) before += v;
-      total += v;
-    }
-    __syncthreads();
-    unsigned long long excl = carry + before + x - sum;
-#pragma unroll
-    for (uint32_t k = 0; k < PER; k++)
-      if (i0 + k < ntiles) {
-        offs[i0 + k] = excl;
-        excl += c[k];
-      }
-    carry += total;
-  }
-  if (threadIdx.x == 0) *total_out = carry;
-}
-
 __global__ void __launch_bounds__(TC_THREADS) k_cbor_parse(CborSpan s, uint64_t lo, const uint64_t* __restrict__ cand,
                                                            uint64_t t, uint32_t tau, int8_t* __restrict__ input_mv,
                                                            int8_t* __restrict__ mv, uint8_t* __restrict__ has_write,
@@ -183,10 +140,6 @@ static bool grids_fit(std::initializer_list<uint64_t> grids) {
     if (!g || g > 0x7FFFFFFFull) return false;
   return true;
 }
-static hipError_t scan(hipStream_t st, const uint32_t* counts, uint64_t n, uint64_t* offs, uint64_t* total) {
-  hipLaunchKernelGGL(k_cbor_tile_scan, dim3(1), dim3(TC_THREADS), 0, st, counts, n, offs, total);
-  return hipGetLastError();
-}
 // mark, scan and compact: the first cap[q] candidates of each kind from lo on
 // into cand[q], the number of all of them into *total[q]. Nothing is launched
 // behind a scan that failed to launch.
@@ -198,7 +151,7 @@ static hipError_t mark_and_compact(hipStream_t st, const CborSpan& s, uint64_t l
   for (int q = 0; q < KINDS; q++) a.counts[q] = counts[q], a.cap[q] = cap[q];
   hipLaunchKernelGGL((k_cbor_marks<KINDS, false>), dim3((uint32_t)ntiles), dim3(TC_THREADS), 0, st, s, lo, a);
   for (int q = KINDS; q-- > 0;) {
-    if (const hipError_t e = scan(st, counts[q], ntiles, offs[q], total[q]); e != hipSuccess) return e;
+    if (const hipError_t e = cbor_scan(st, counts[q], ntiles, offs[q], total[q]); e != hipSuccess) return e;
     a.counts[q] = nullptr, a.offs[q] = offs[q], a.cand[q] = cand[q];
   }
   hipLaunchKernelGGL((k_cbor_marks<KINDS, true>), dim3((uint32_t)ntiles), dim3(TC_THREADS), 0, st, s, lo, a);
@@ -243,7 +196,7 @@ hipError_t launch_blocks_cbor_decode(hipStream_t st, const uint8_t* d_bytes, uin
   if ((e = mark_and_compact<2>(st, s, first_off, ntiles, counts, offs, cand, cap, total)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_cbor_block_heads, dim3((uint32_t)bgrid), dim3(TC_THREADS), 0, st, s, first_off, cand[1], B, tau, T,
                      verdict);
-  if ((e = scan(st, T.n_steps, B, T.step_start, &verdict->t)) != hipSuccess) return e;
+  if ((e = cbor_scan(st, T.n_steps, B, T.step_start, &verdict->t)) != hipSuccess) return e;
   hipLaunchKernelGGL(k_cbor_block_steps, dim3((uint32_t)sgrid), dim3(TC_THREADS), 0, st, s, cand[0], t_max, B,
                      T.step_start, tau, input_mv, mv, has_write, wsym, ends, verdict);
   hipLaunchKernelGGL(k_cbor_block_chain, dim3((uint32_t)bgrid), dim3(TC_THREADS), 0, st, s, cand[1], cand[0], t_max, B, tau,

@@ -268,7 +268,19 @@ int cmd_prove_trace(const Args& a) {
       break;
     }
     const uint32_t nblk = (uint32_t)((tv.t + b - 1) / b);
-    if (!a.out_blocks.empty()) {
+    if (!a.out_blocks.empty() && ext_lower(a.out_blocks) == "cbor" && !a.host_decode) {
+      // written on the device from the resident image: only the file's bytes
+      // come home (sezkp_ctx_encode_trace_blocks_cbor; adopted by DESIGN §14's
+      // measurement). --host-decode keeps the former order throughout.
+      sezkp_buf buf{};
+      if (sezkp_ctx_encode_trace_blocks_cbor(ctx, &buf, msg, sizeof msg)) {
+        fprintf(stderr, "Error: %s\n", msg);
+        break;
+      }
+      std::vector<uint8_t> out(buf.data, buf.data + buf.len);
+      sezkp_buf_free(&buf);
+      if (!write_file(a.out_blocks, out, err)) { fprintf(stderr, "Error: %s\n", err.c_str()); break; }
+    } else if (!a.out_blocks.empty()) {
       sezkp_blocks* bh = nullptr;
       // decoded on the device: the steps come back from there (NULL steps)
       if (sezkp_ctx_trace_blocks(ctx, by_bytes ? nullptr : &tv, &bh, msg, sizeof msg)) {

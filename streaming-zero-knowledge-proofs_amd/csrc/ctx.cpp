@@ -238,6 +238,7 @@ sezkp_ctx::~sezkp_ctx() {
   audit.release();
   vfy.release();
   cbuf.release();
+  enc.release();
   dict.release();
   for (auto& e : ev)
     if (e) (void)hipEventDestroy(e);

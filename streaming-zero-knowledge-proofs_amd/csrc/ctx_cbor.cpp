@@ -104,6 +104,14 @@ void sezkp_ctx::cbor_claim() {
   bcbor.drop_pending();
 }
 
+void sezkp_ctx::cbor_stage_block() {
+  if (cbuf.h_stage) return;
+  void* q = nullptr;
+  HIP_OR_THROW(hipHostMalloc(&q, 2 * CborBuffers::STAGE_HALF, hipHostMallocDefault));
+  cbuf.h_stage = static_cast<uint8_t*>(q);
+  for (auto& e : cbuf.stage_ev) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
+}
+
 void sezkp_ctx::cbor_bytes_to_device(const uint8_t* data, size_t len) {
   for (auto& e : cbuf.ev)
     if (!e) HIP_OR_THROW(hipEventCreate(&e));
@@ -114,12 +122,7 @@ void sezkp_ctx::cbor_bytes_to_device(const uint8_t* data, size_t len) {
     copy_chunked(cbuf.d_bytes, data, len, COPY_CHUNK, hipMemcpyHostToDevice, st);
   } else {
     constexpr size_t H = CborBuffers::STAGE_HALF;
-    if (!cbuf.h_stage) {
-      void* q = nullptr;
-      HIP_OR_THROW(hipHostMalloc(&q, 2 * H, hipHostMallocDefault));
-      cbuf.h_stage = static_cast<uint8_t*>(q);
-      for (auto& e : cbuf.stage_ev) HIP_OR_THROW(hipEventCreateWithFlags(&e, hipEventDisableTiming));
-    }
+    cbor_stage_block();
     size_t k = 0;
     for (size_t o = 0; o < len; k++) {
       const size_t n = std::min(H, len - o), half = k & 1;

@@ -1,6 +1,7 @@
 // prover_ctx.h — the prover context (struct sezkp_ctx) and what its units
 // share: ctx.cpp (life of a context), ctx_upload.cpp, ctx_trace.cpp,
-// ctx_cbor.cpp (trace and block files decoded on the device), ctx_services.cpp
+// ctx_cbor.cpp (trace and block files decoded on the device), ctx_encode.cpp
+// (the same files written on the device), ctx_services.cpp
 // (audit, batch verify), proof_run.cpp (one proof) and the C ABI in
 // abi_ctx.cpp / abi_kernels.cpp. Internal to the library: nothing
 // outside csrc/ includes it.
@@ -73,7 +74,8 @@ struct AsyncSlot {
 //                      context (ctx_create), SEZKP_VERIFY_CHUNK_BYTES per verify
 //                      call (verify_batch), SEZKP_TRACE_CBOR_HOST per trace-file
 //                      decode (decode_trace_cbor_device), SEZKP_BLOCKS_CBOR_HOST per
-//                      block-file decode (decode_blocks_cbor_device)
+//                      block-file decode (decode_blocks_cbor_device), SEZKP_CBOR_ENCODE_HOST
+//                      per encode call (ctx_encode.cpp)
 struct ProveOptions {
   bool host_trace = false;   // SEZKP_HOST_TRACE=1: host-side marks printed per proof
   bool sync_debug = false;   // SEZKP_SYNC_DEBUG: sync after every launch, to name the failing kernel
@@ -283,6 +285,37 @@ struct BlocksCborIngest {
     pending = false;
     pend = BlockStore();
   }
+};
+// CBOR files encoded on the device (ctx_encode.cpp, cbor_encode.hip): the
+// file image, the tile and block words of the length passes, the block
+// tables and the step arrays of a view that came from the host, the two
+// totals and their pinned landing place. The context's own, apart from
+// CborBuffers (an encode leaves a pending ingest alone) but for the pinned
+// staging block, which the file's bytes come home through. Grown on demand
+// and kept.
+struct EncodeBuffers {
+  uint8_t* d_out = nullptr;
+  size_t out_cap = 0;
+  uint32_t* d_counts = nullptr;  // step bytes per tile
+  size_t counts_cap = 0;
+  uint64_t* d_offs = nullptr;
+  size_t offs_cap = 0;
+  uint32_t* d_blen = nullptr;  // head + tail bytes per block
+  size_t blen_cap = 0;
+  uint64_t* d_pre = nullptr;
+  size_t pre_cap = 0;
+  uint64_t* d_first = nullptr;
+  size_t first_cap = 0;
+  uint8_t* d_tables = nullptr;  // a view's block fields and step_start
+  size_t tables_cap = 0;
+  uint8_t* d_steps = nullptr;  // a view's host step arrays
+  size_t steps_cap = 0;
+  uint64_t* d_words = nullptr;
+  uint64_t* h_words = nullptr;  // pinned
+  hipEvent_t ev[5]{};           // around the length kernels, around the emit kernels, after the copy home
+  sezkp_encode_info info{};
+  bool have_info = false;
+  void release();
 };
 // a device block of at least `bytes` bytes: kept when large enough, else
 // replaced by one a quarter larger than asked for (contents undefined)
@@ -553,6 +586,15 @@ struct sezkp_ctx {
   SEZKP_LOCAL bool decode_blocks_cbor_device(const uint8_t* data, size_t len, BlockStore& out, sezkp_block_view& steps);
   void ingest_blocks_cbor(const uint8_t* data, size_t len);  // decode into bcbor.pend
   void upload_ingested();                                    // upload() of the pending ingest, which it drops
+  // ---- CBOR files encoded on the device (ctx_encode.cpp). Each returns the
+  // file in malloc'd memory (*data, *len: a sezkp_buf's) and leaves its report
+  // in enc.info.
+  EncodeBuffers enc;
+  void encode_trace_blocks_cbor(sezkp_buf* out);                  // the active trace image's blocks file
+  void encode_blocks_cbor(const sezkp_block_view& v, sezkp_buf* out);
+  void encode_trace_cbor(const sezkp_trace_view* tv, sezkp_buf* out);  // null: the active trace image
+  // the pinned staging block of two halves and its events, once
+  SEZKP_LOCAL void cbor_stage_block();
 
   static void* take_spare(std::multimap<size_t, void*>& m, size_t bytes) {
     auto it = m.find(bytes);

@@ -251,6 +251,22 @@ hipError_t launch_blocks_cbor_decode(hipStream_t st, const uint8_t* d_bytes, uin
                                      uint64_t* const offs[2], uint64_t* const cand[2], uint64_t* ends,
                                      const BlocksCborTables& T, int8_t* input_mv, int8_t* mv, uint8_t* has_write,
                                      uint16_t* wsym, BlocksCborVerdict* verdict);
+// A block file or a TraceFile written as CBOR on the device (cbor_encode.hip,
+// cbor_emit_plan.h), in two halves with the host between them, which sizes the
+// file's memory by the length that comes home. Lengths: the step lengths per
+// tile (counts / offs: cbor_emit_tiles words), the head and tail lengths per
+// block (blen / pre: B words), both scanned; words[0] = all step bytes,
+// words[1] = all head and tail bytes. Emit: the steps, then the heads and
+// tails, into out[0, out_len); first: B words.
+struct CborEmitShape;
+struct CborEmitSteps;
+struct CborEmitTables;
+hipError_t launch_cbor_emit_lengths(hipStream_t st, const CborEmitShape& sh, const CborEmitSteps& A,
+                                    const CborEmitTables& T, uint32_t* counts, uint64_t* offs, uint32_t* blen,
+                                    uint64_t* pre, uint64_t* words);
+hipError_t launch_cbor_emit(hipStream_t st, const CborEmitShape& sh, const CborEmitSteps& A, const CborEmitTables& T,
+                            const uint64_t* offs, const uint32_t* blen, const uint64_t* pre, uint64_t* first,
+                            uint64_t steps_total, uint8_t* out, uint64_t out_len);
 
 // Per-row constraint sums of the composition (k_compose_terms): everything
 // of C(i) that does not depend on the transcript, summed over the tapes

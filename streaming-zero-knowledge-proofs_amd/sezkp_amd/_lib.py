@@ -50,6 +50,8 @@ EXPORTS = [
     "sezkp_ctx_decode_blocks_cbor", "sezkp_stark_v1_prove_blocks_cbor", "sezkp_blocks_cbor_head",
     "sezkp_ctx_blocks_ingest_stats",
     "sezkp_ctx_lde_closed_stages",
+    "sezkp_ctx_encode_trace_blocks_cbor", "sezkp_ctx_encode_blocks_cbor", "sezkp_ctx_encode_trace_cbor",
+    "sezkp_ctx_encode_stats",
 ]
 
 AIR_FAMILIES = ("mv_domain", "head_range", "slack_range", "sym_range", "boundary")  # SEZKP_AIR_FAMILIES order
@@ -116,6 +118,16 @@ class BlocksIngestInfo(C.Structure):  # sezkp_blocks_ingest_info
     _fields_ = [("path", C.c_uint32), ("reason", C.c_uint32), ("index", C.c_uint64), ("bytes", C.c_uint64),
                 ("n_blocks", C.c_uint32), ("tau", C.c_uint32), ("t", C.c_uint64), ("block_candidates", C.c_uint64),
                 ("step_candidates", C.c_uint64), ("ms_h2d", C.c_double), ("ms_decode", C.c_double),
+                ("ms_host", C.c_double)]
+
+
+# sezkp_encode_info: the reason by its SEZKP_ENCODE_R_* value
+ENCODE_REASONS = ("none", "forced", "empty")
+
+
+class EncodeInfo(C.Structure):  # sezkp_encode_info
+    _fields_ = [("path", C.c_uint32), ("reason", C.c_uint32), ("bytes", C.c_uint64), ("t", C.c_uint64),
+                ("tau", C.c_uint32), ("n_blocks", C.c_uint32), ("ms_kernels", C.c_double), ("ms_d2h", C.c_double),
                 ("ms_host", C.c_double)]
 
 
@@ -292,6 +304,10 @@ def _load():
     L.sezkp_blocks_cbor_head.argtypes = [C.c_void_p, C.c_size_t, C.POINTER(C.c_uint32), C.POINTER(C.c_uint32),
                                          C.POINTER(C.c_uint64)]
     L.sezkp_ctx_blocks_ingest_stats.argtypes = [C.c_void_p, C.POINTER(BlocksIngestInfo)]
+    L.sezkp_ctx_encode_trace_blocks_cbor.argtypes = [C.c_void_p, C.POINTER(Buf)] + E
+    L.sezkp_ctx_encode_blocks_cbor.argtypes = [C.c_void_p, C.POINTER(BlockView), C.POINTER(Buf)] + E
+    L.sezkp_ctx_encode_trace_cbor.argtypes = [C.c_void_p, C.POINTER(TraceView), C.POINTER(Buf)] + E
+    L.sezkp_ctx_encode_stats.argtypes = [C.c_void_p, C.POINTER(EncodeInfo)]
     return L
 
 

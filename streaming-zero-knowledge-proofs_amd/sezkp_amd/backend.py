@@ -13,7 +13,7 @@ from dataclasses import dataclass, field
 
 from ._lib import (AIR_FAMILIES, INGEST_PATHS, INGEST_REASONS, SEZKP_FLAG_ROOT_FROM_TRACE, SEZKP_FLAG_STREAMING,
                    VERIFY_TIMES, AirAuditC, Buf, ProofRef, SezkpError, TraceIngestInfo, BlocksIngestInfo, BLOCKS_INGEST_REASONS, VerifyResultC, check, lib,
-                   take_buf)
+                   take_buf, ENCODE_REASONS, VIEW_FIELDS, EncodeInfo)
 from .blocks import BlockSoA
 from .trace import Trace, cbor_bytes, trace_view
 
@@ -456,6 +456,68 @@ class ProverContext:
         err = C.create_string_buffer(1024)
         check(lib.sezkp_ctx_trace_blocks(self._h, None, C.byref(h), err, 1024), err)
         return BlockSoA._take(h)
+
+    def blocks_cbor(self) -> bytes:
+        """The blocks file (blocks.cbor) of the trace image, written on the
+        device (sezkp_ctx_encode_trace_blocks_cbor): the bytes of
+        `blocks().to_cbor()`, with no step array read back to the host."""
+        b = Buf()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_encode_trace_blocks_cbor(self._h, C.byref(b), err, 1024), err)
+        return take_buf(b)
+
+    def encode_blocks_cbor(self, blocks: BlockSoA, steps=None) -> bytes:
+        """`blocks.to_cbor()` written on the device (sezkp_ctx_encode_blocks_cbor).
+        steps: (input_mv, mv, has_write, wsym) to take in place of the step
+        arrays of `blocks`, numpy arrays or contiguous torch tensors on this
+        context's device (see trace.trace_view); `blocks` may then be a
+        metadata-only BlockSoA. Needs no uploaded trace."""
+        v = blocks.view()
+        keep = None
+        if steps is None:
+            blocks.check_shape()
+        else:
+            blocks.check_shape(int(blocks.input_mv.size))  # its own step arrays are not read
+            tv, keep = trace_view(*steps, b=0, device=getattr(self, "device", None))
+            if int(tv.tau) != blocks.tau or int(tv.t) != int(blocks.step_start[-1] if blocks.n_blocks else 0):
+                raise SezkpError(-1, "encode_blocks_cbor: the step arrays given are of another shape than the blocks")
+            for f, _t in VIEW_FIELDS[-4:]:
+                setattr(v, f, C.cast(C.c_void_p(getattr(tv, f)), type(getattr(v, f))))
+        b = Buf()
+        err = C.create_string_buffer(1024)
+        check(lib.sezkp_ctx_encode_blocks_cbor(self._h, C.byref(v), C.byref(b), err, 1024), err)
+        del keep  # the call is synchronous
+        return take_buf(b)
+
+    def trace_cbor(self, trace=None) -> bytes:
+        """A TraceFile (version 1, no meta) written on the device
+        (sezkp_ctx_encode_trace_cbor): of the trace image when `trace` is None,
+        else of a Trace or of (input_mv, mv, has_write, wsym), numpy arrays or
+        contiguous torch tensors on this context's device. The bytes of
+        `Trace.to_cbor()`."""
+        b = Buf()
+        err = C.create_string_buffer(1024)
+        if trace is None:
+            check(lib.sezkp_ctx_encode_trace_cbor(self._h, None, C.byref(b), err, 1024), err)
+            return take_buf(b)
+        arrs = trace.arrays() if isinstance(trace, Trace) else tuple(trace)
+        v, keep = trace_view(*arrs, b=0, device=getattr(self, "device", None))
+        check(lib.sezkp_ctx_encode_trace_cbor(self._h, C.byref(v), C.byref(b), err, 1024), err)
+        del keep  # the call is synchronous
+        return take_buf(b)
+
+    def encode_stats(self) -> dict:
+        """What the last blocks_cbor / encode_blocks_cbor / trace_cbor call did
+        (sezkp_ctx_encode_stats): path "device" or "host", the reason the host
+        wrote the file ("none" when it did not), bytes, t, tau, n_blocks, and
+        the times ms_kernels, ms_d2h (HIP events) and ms_host."""
+        i = EncodeInfo()
+        rc = lib.sezkp_ctx_encode_stats(self._h, C.byref(i))
+        if rc != 0:
+            raise SezkpError(rc, "encode_stats: no encode call on this context yet, or a proof is in flight")
+        return {"path": INGEST_PATHS[i.path], "reason": ENCODE_REASONS[i.reason], "bytes": int(i.bytes), "t": int(i.t),
+                "tau": int(i.tau), "n_blocks": int(i.n_blocks), "ms_kernels": i.ms_kernels, "ms_d2h": i.ms_d2h,
+                "ms_host": i.ms_host}
 
     def upload_rows(self, blocks: BlockSoA, row0: int, nrows: int) -> None:
         """Upload from a view whose step arrays hold only rows [row0, row0 +
